@@ -11,9 +11,17 @@ timed region.
 Output: one JSON line (rank 0).  `roofline.achieved` = 48 algorithmic bytes per
 (replica, element) join x cells per launch / average launch time measured with HIP
 events on the engine's stream; `roofline.traffic` = HBM bytes per launch from the
-rocprofv3 PMC passes committed under profiles/ (null if absent);  `cpu_baseline` =
-the C restatement of lasp_orset:merge/2 (oracle/laspj_oracle.c, kind "port") timed on
-this host's cores on a bounded sample.
+rocprofv3 PMC passes committed under profiles/ (null if absent).
+
+A plain run does only what the headline needs: set up, warm up, time `--steps` joins,
+write `--dump-outputs` if asked, print the line.  `--full` adds every other leg to the
+same line: `config1_gpu` (with `steady`), `join_t128`, `config5_list_bind`, the
+anti-entropy leg when N > 1, and `cpu_baseline` = the C restatement of
+lasp_orset:merge/2 (oracle/laspj_oracle.c, kind "port") timed on this host's cores on a
+bounded sample.
+
+`--dump-outputs DIR` writes a fixed, seeded sample of the last timed join's result
+(see dump_outputs) so that two builds can be compared cell for cell.
 """
 
 from __future__ import annotations
@@ -38,15 +46,23 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline join: config 1 on the "
+                         "device, the steady state, the T = 128 join, the list re-bind, the "
+                         "CPU baseline and (N > 1) anti-entropy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed join's result as "
+                         "DIR/<name>.npy")
     ap.add_argument("--replicas", type=int, default=1 << 20, help="replica pairs per GPU")
     ap.add_argument("--elements", type=int, default=4096)
     ap.add_argument("--wide-replicas", type=int, default=1 << 19,
-                    help="replicas of the T = 128 join leg (0: skip it)")
+                    help="replicas of the T = 128 join leg of --full (0: skip it)")
     ap.add_argument("--list-leg", type=int, default=1,
-                    help="1: time config 5's list re-bind and the Store update (rank 0, N=1)")
+                    help="1: --full times config 5's list re-bind and the Store update "
+                         "(rank 0, N=1)")
     ap.add_argument("--cpu-budget", type=float, default=12.0,
-                    help="seconds of CPU baseline work (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="seconds of CPU baseline work under --full (rank 0, N=1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--dry-run", action="store_true",
                     help="check the launch (ranks, world size) and exit before any GPU work")
     ap.add_argument("--grid", type=int, default=0)
@@ -55,7 +71,7 @@ def parse():
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "r06_pmc_join.json"),
                     help="PMC summary giving HBM traffic per join launch")
     ap.add_argument("--antientropy", choices=["auto", "on", "off"], default="auto",
-                    help="config-3 gossip anti-entropy leg (auto: when N > 1)")
+                    help="config-3 gossip anti-entropy leg (auto: with --full when N > 1)")
     ap.add_argument("--ae-objects", type=int, default=1 << 20,
                     help="objects per GPU for the anti-entropy leg: BASELINE config 3, "
                          "2^20 x 4096 = 64 GiB of state (+ 64 GiB receive buffer)")
@@ -884,6 +900,48 @@ def list_leg(ctx):
     return out
 
 
+DUMP_ROWS = 256              # replicas sampled by --dump-outputs
+DUMP_BYTES = 48 << 20        # ceiling on what --dump-outputs writes
+DUMP_SEED = 0x4C415350
+
+
+def dump_rows(replicas: int, elements: int):
+    """The replicas --dump-outputs samples: the first two, the last two and seeded picks
+    in between, ascending; all of them when the batch is small.  The same for every run
+    with the same --replicas / --elements."""
+    import numpy as np
+    n = max(1, min(DUMP_ROWS, DUMP_BYTES // (32 * elements), replicas))
+    if n >= replicas:
+        return np.arange(replicas, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    ends = [r for r in (0, 1, replicas - 2, replicas - 1) if 0 <= r < replicas][:n]
+    picks = dict.fromkeys(ends)
+    for r in rng.choice(replicas, size=n, replace=False):
+        if len(picks) == n:
+            break
+        picks.setdefault(int(r))
+    return np.array(sorted(picks), dtype=np.int64)
+
+
+def dump_outputs(path: str, c):
+    """What the timed join left in C, for the sampled replicas (dump_rows):
+    `join_cells.npy`, float64 (rows, E, 2, 2) — per element slot the cell's {p, r} masks,
+    each as [low 32 bits, high 32 bits] so that every value is exact in float64 — and
+    `join_rows.npy`, the sampled replica indices.  In a multi-GPU run rank 0 alone writes
+    (its own shard), so the files stay under the ceiling whatever N is."""
+    import numpy as np
+    rows = dump_rows(c.replicas, c.elements)
+    ne = min(c.elements, DUMP_BYTES // 32)       # (a row wider than the ceiling: its head)
+    cells = np.empty((len(rows), ne, 2, 2), dtype=np.float64)
+    for k, r in enumerate(rows):
+        w = c.download(int(r), 1)[0, :ne]
+        cells[k, :, :, 0] = w & np.uint64(0xFFFFFFFF)
+        cells[k, :, :, 1] = w >> np.uint64(32)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "join_cells.npy"), cells)
+    np.save(os.path.join(path, "join_rows.npy"), rows.astype(np.float64))
+
+
 def load_traffic(path: str, replicas: int, elements: int):
     try:
         with open(path) as f:
@@ -919,6 +977,9 @@ def main():
     if args.gpus < 1:
         print("bench: --gpus must be >= 1", file=sys.stderr)
         sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        sys.exit(2)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -932,7 +993,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
-    ae_on = args.antientropy == "on" or (args.antientropy == "auto" and world > 1)
+    full = args.full
+    ae_on = args.antientropy == "on" or (args.antientropy == "auto" and world > 1 and full)
     if world > 1 or ae_on:
         # torch first: its bundled HIP runtime is then the one liblaspj binds to
         import torch
@@ -990,15 +1052,20 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
 
-    # the per-call legs run at N = 1 only: with more ranks, rank 0's host-side legs would
-    # outlast the other ranks' anti-entropy guard (--ae-timeout) while they wait for it
-    cfg1 = config1_gpu(ctx) if rank == 0 and world == 1 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, c)
+
+    # everything below the headline runs under --full only.  The per-call legs run at
+    # N = 1 only: with more ranks, rank 0's host-side legs would outlast the other ranks'
+    # anti-entropy guard (--ae-timeout) while they wait for it
+    legs = full and rank == 0 and world == 1
+    cfg1 = config1_gpu(ctx) if legs else None
     if cfg1 is not None:
         cfg1["steady"] = steady_leg(ctx)
     del a, b, c                          # free the 192 GiB of join operands first
     ctx.synchronize()
-    wide = wide_leg(ctx, args) if rank == 0 and world == 1 and args.wide_replicas else None
-    lists = list_leg(ctx) if rank == 0 and world == 1 and args.list_leg else None
+    wide = wide_leg(ctx, args) if legs and args.wide_replicas else None
+    lists = list_leg(ctx) if legs and args.list_leg else None
 
     out = None
     if rank == 0:
@@ -1067,7 +1134,7 @@ def main():
         _final_barrier(dist)
         return
 
-    if world == 1 and not args.no_cpu:
+    if full and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(E, args.cpu_budget)
         steady = out.get("config1_gpu", {}).get("steady")
         if isinstance(steady, dict):
