@@ -998,6 +998,53 @@ int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_
                          const uint8_t** err_elem, uint64_t* err_len, const uint8_t** minted,
                          uint32_t* nminted, int32_t* verdict);
 
+/* Blocking reads kept beside the variable: `#dv.waiting_threads` (include/lasp.hrl:60-63)
+ * on the device.  A waiter is {id, strict, Threshold}; its threshold is decoded once, when
+ * it is registered, into cells of the variable's namespace (they follow the namespace as
+ * the variable's own cells do: widened, grown, written out and decoded again across a
+ * dictionary reset), and its image is kept on the host.  `id` is opaque (the NIF maps it to
+ * a pid / ref); the same id may wait twice, and equal thresholds are not merged.  bind,
+ * bind_many, update, union and write do not re-check by themselves: the NIF calls
+ * laspj_var_recheck / laspj_var_recheck_many after a call that answered WRITTEN /
+ * UPDATE_OK; every call here is serialised by the context and enqueued on its stream
+ * behind the writes before it.
+ *
+ * read/6 (lasp_core.erl:331-364): threshold_met(Type, #dv.value, Threshold)
+ * (lasp_lattice.erl:62-75) answered as laspj_var_etf_threshold answers it; met -> *met = 1
+ * and nothing is kept; otherwise *met = 0 and the waiter is appended to the variable's
+ * waiting_threads (strict = 1: {strict, Threshold}; the caller has replaced `undefined`
+ * by Type:new(), whose image is []).  verdict FALLBACK (a host-held value, a threshold the
+ * namespace cannot represent): nothing is registered. */
+int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict,
+                   uint64_t id, int32_t* met, int32_t* verdict);
+/* write/4's reply_to_all (lasp_core.erl:839-844, 765-825): every waiter of the variable
+ * checked against its value in one device pass (lasp_lattice.erl:62-75, 137-161,
+ * 212-253).  ids[0 .. *nmet) receives the ids of the waiters now met, in registration
+ * order (the order reply_to_all replies in); they are removed, the others stay in their
+ * order (`StillWaiting0 ++ [H]`), *nwaiting of them.  More than cap met: nothing is
+ * removed, *nmet > cap says how much room to come back with.  A variable with no waiters
+ * does no device work.  verdict FALLBACK (a host-held value): nothing fires or is removed;
+ * the NIF walks the waiters (laspj_var_waiter_at), runs the reference's clause over the
+ * read value and cancels those it replied to. */
+int laspj_var_recheck(laspj_var* var, uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                      uint32_t* nwaiting, int32_t* verdict);
+/* the same after laspj_var_etf_bind_many / a vnode's queued writes (lasp_vnode.erl:213-237;
+ * lasp_core.erl:765-825 per variable): all waiters of n distinct variables of one context
+ * in one device pass; ids grouped by variable in argument order, nmet[i] and verdict[i]
+ * per variable.  More than cap met over all of them: nothing is removed. */
+int laspj_var_recheck_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars, uint64_t* ids,
+                           uint32_t cap, uint32_t* nmet, int32_t* verdict);
+/* a waiter leaves before it was met (its process died: the first waiter with that id of
+ * `#dv.waiting_threads`, include/lasp.hrl:60-63); *found 0 when there is none */
+int laspj_var_wait_cancel(laspj_var* var, uint64_t id, int32_t* found);
+/* length(`#dv.waiting_threads`) (include/lasp.hrl:60-63) */
+int laspj_var_waiter_count(const laspj_var* var, uint32_t* n);
+/* the k-th waiter in list order (lasp_core.erl:765-825 walks them so): its id, strict and
+ * its threshold image as registered (valid until the variable's next waiter call);
+ * LASPJ_E_RANGE past the last */
+int laspj_var_waiter_at(laspj_var* var, uint32_t k, uint64_t* id, int32_t* strict,
+                        const uint8_t** threshold, uint64_t* n);
+
 /* counters of this context's NIF path: [0] calls, [1] device passes, [2] dictionary
  * registrations, [3] dictionary resets, [4] device image rebuilds, [5] host-encoded passes
  * (token images of mixed lengths), [6] FALLBACK verdicts, [7] dictionary elements (both

@@ -87,6 +87,10 @@ extern "C" {
 #define LASPJ_TUNE_LIST_CHUNK   15   /* rows per chunk of the list merges' chunked walk
                                         (0 = default: 1024, or more to keep <= 1024
                                         chunks; 64 .. 2^20)                             */
+#define LASPJ_TUNE_WAITER_FINISH 16   /* laspj_var_recheck's met flags: 0 = default (the
+                                        one-block finish launch behind the check), 1 = that
+                                        finish launch, 2 = written by the check's
+                                        last-arriving block (ticket counter); for A/B   */
 int         laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value);
 
 #ifdef __cplusplus

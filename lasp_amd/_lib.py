@@ -42,6 +42,7 @@ TUNE_ETF_SEG = 9
 TUNE_LIST_WALK = 10
 TUNE_NIF_PASSES = 14
 TUNE_LIST_CHUNK = 15
+TUNE_WAITER_FINISH = 16
 NIF_OK, NIF_FALLBACK = 0, 1           # verdicts of the NIF-level entry points
 NIF_STATS = 20
 
@@ -242,6 +243,14 @@ SIGNATURES = {
     "laspj_var_union": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,
                                  C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_var_wait": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_var_recheck": (i, [vp, vp, u32, C.POINTER(u32), C.POINTER(u32),
+                              C.POINTER(C.c_int32)]),
+    "laspj_var_recheck_many": (i, [vp, u32, vp, vp, u32, vp, vp]),
+    "laspj_var_wait_cancel": (i, [vp, u64, C.POINTER(C.c_int32)]),
+    "laspj_var_waiter_count": (i, [vp, C.POINTER(u32)]),
+    "laspj_var_waiter_at": (i, [vp, u32, C.POINTER(u64), C.POINTER(C.c_int32), vpp,
+                                C.POINTER(u64)]),
     "laspj_list_etf_args": (i, [vp, C.c_int32, vp, u64, vpp, C.POINTER(u64),
                                 C.POINTER(C.c_int32)]),
     "laspj_list_etf_map": (i, [vp, C.c_int32, vp, u64, vp, u64, vpp, C.POINTER(u64),

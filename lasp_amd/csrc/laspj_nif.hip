@@ -85,6 +85,17 @@ struct KindState {
     WideDict* wd = nullptr;
 };
 
+// One entry of `#dv.waiting_threads` ({threshold, read, From, Type, Threshold},
+// lasp_core.erl:331-364): the threshold decoded once into `cells`, a hidden variable of the
+// waiting variable's namespace (registered where variables are, so widening, growth and a
+// dictionary reset carry it along), and its image as registered.
+struct Waiter {
+    uint64_t id = 0;
+    int32_t strict = 0;
+    std::vector<uint8_t> image;
+    laspj_var* cells = nullptr;
+};
+
 }  // namespace laspj
 
 // A device-resident variable's value (the `#dv.value` of lasp_core's store): cells over its
@@ -102,6 +113,7 @@ struct laspj_var {
     bool resident = true;            // cells hold the value (else `image` does)
     bool held = false;               // `image` is a value write/4 could not represent
     std::vector<uint8_t> image;      // host-held value (term_to_binary image)
+    std::vector<laspj::Waiter> waiters;   // `#dv.waiting_threads`, in list order
 };
 
 namespace laspj {
@@ -377,6 +389,159 @@ __global__ void __launch_bounds__(256) k_var_union(uint64_t* out, const uint64_t
         }
     }
     if (__ballot(ch) && (threadIdx.x & 63u) == 0) atomicOr(changed, 1u);
+}
+
+// write/4's reply_to_all (lasp_core.erl:839-844, 765-825) over resident variables: every
+// waiter's threshold_met(Type, Value, Threshold) (lasp_lattice.erl:62-75) in one launch.
+// A wave item is (variable, tile of kWaitTile 16-byte units of its value, chunk of
+// kWaitChunk of its waiters): the value's tile is read once into registers and compared
+// with the same units of each waiter of the chunk.  A unit is a {p, r} pair of an OR-Set
+// cell (tw of them per element in a wide namespace) or two bitmap words of a G-Set; units
+// past the end of a block of cells are absent (a waiter registered before its namespace
+// grew covers fewer element slots than the value; null cells — a [] threshold, a variable
+// still holding new() — cover none).
+//   OR-Set (lasp_lattice.erl:153-161): violation = some cell has pP & ~pC; strict
+//     (:235-253) also needs a common element's cell to differ, removed flags included
+//     (`Ids =/= Ids1`), or np < nc (which is also the [] -> non-empty clause)
+//   wide: the same per {p, r} pair; strict = and some pair differs
+//   G-Set (:137-140, 212-215): violation = p & ~c; strict also needs the words to differ
+// Records (zeroed ahead of the launch): per waiter {flags: 1 violation, 2 changed; np},
+// per variable nc (a property of the value alone: counted by the first chunk's waves);
+// device-scope atomics, one per wave and nonzero result.  The met flags are written to
+// the pinned answer area by a one-block finish launch, or (FUSED) by the block whose
+// ticket shows it arrived last.
+constexpr uint32_t kWaitTile = 128;     // units per wave item: two per lane
+constexpr uint32_t kWaitChunk = 16;     // waiters per wave item
+constexpr uint32_t kWaitNarrow = 0, kWaitWide = 1, kWaitGset = 2;
+struct WaitVar {
+    const uint64_t* cells;
+    uint32_t words;                     // u64 words of `cells`
+    uint32_t mode;
+    uint32_t w0, nw;                    // its waiters: WaitDesc [w0, w0 + nw)
+    uint64_t item0;                     // its first wave item
+};
+struct WaitDesc {
+    const uint64_t* cells;
+    uint32_t words;
+    uint32_t var_strict;                // variable index << 1 | strict
+};
+static_assert(sizeof(WaitVar) == 32 && sizeof(WaitDesc) == 16, "descriptor layout");
+typedef unsigned long long wait2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ wait2 wait_ld(const uint64_t* base, uint64_t q, uint32_t words) {
+    wait2 v = {0ull, 0ull};
+    if (2 * q + 1 < words) v = *reinterpret_cast<const wait2*>(base + 2 * q);
+    else if (2 * q < words) v.x = base[2 * q];
+    return v;
+}
+
+__device__ __forceinline__ void wait_finish(uint32_t j, const WaitVar* vars, const WaitDesc* ws,
+                                            uint32_t* rec, uint32_t* nc, uint8_t* met) {
+    const uint32_t vs = ws[j].var_strict, v = vs >> 1;
+    const uint32_t f = __hip_atomic_load(rec + 2 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t np = __hip_atomic_load(rec + 2 * j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t ncv = __hip_atomic_load(nc + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool infl = !(f & 1u);
+    bool res = infl;
+    if (vs & 1u) res = infl && ((f & 2u) || (vars[v].mode == kWaitNarrow && np < ncv));
+    met[j] = res ? 1 : 0;
+}
+
+template <bool FUSED>
+__global__ void __launch_bounds__(256) k_waiter_check(const WaitVar* vars, uint32_t nv,
+                                                      const WaitDesc* ws, uint32_t nws,
+                                                      uint64_t items, uint32_t* ticket,
+                                                      uint32_t* rec, uint32_t* nc, uint8_t* met) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = (uint64_t)gridDim.x * 4;
+    for (uint64_t s = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6; s < items; s += nwaves) {
+        uint32_t lo = 0, hi = nv;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (vars[mid].item0 <= s) lo = mid;
+            else hi = mid;
+        }
+        const WaitVar V = vars[lo];
+        const uint32_t nch = (V.nw + kWaitChunk - 1) / kWaitChunk;
+        const uint64_t local = s - V.item0, tile = local / nch;
+        const uint32_t ch = (uint32_t)(local - tile * nch);
+        const uint64_t q0 = tile * kWaitTile + lane, q1 = q0 + 64;
+        const wait2 c0 = wait_ld(V.cells, q0, V.words), c1 = wait_ld(V.cells, q1, V.words);
+        if (ch == 0 && V.mode == kWaitNarrow) {
+            const uint32_t n = __popcll(__ballot(c0.x != 0)) + __popcll(__ballot(c1.x != 0));
+            if (lane == 0 && n) atomicAdd(nc + lo, n);
+        }
+        const uint32_t j0 = V.w0 + ch * kWaitChunk, j1 = min(V.w0 + V.nw, j0 + kWaitChunk);
+        // the chunk's descriptors: one per lane, handed round by shuffles
+        uint64_t dp = 0;
+        uint32_t dw = 0;
+        if (j0 + lane < j1) {
+            dp = reinterpret_cast<uint64_t>(ws[j0 + lane].cells);
+            dw = ws[j0 + lane].words;
+        }
+        for (uint32_t j = j0; j < j1; j += 4) {
+            wait2 p0[4], p1[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // (lanes past the chunk hold no words: nothing is read for them)
+                const auto* P = reinterpret_cast<const uint64_t*>(
+                    (uint64_t)__shfl((unsigned long long)dp, (int)(j + k - j0), 64));
+                const uint32_t w = __shfl(dw, (int)(j + k - j0), 64);
+                p0[k] = wait_ld(P, q0, w);
+                p1[k] = wait_ld(P, q1, w);
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                if (j + k >= j1) break;
+                const wait2 a = p0[k], b = p1[k];
+                bool viol, changed;
+                uint32_t np = 0;
+                if (V.mode == kWaitNarrow) {
+                    viol = ((a.x & ~c0.x) | (b.x & ~c1.x)) != 0;
+                    changed = ((a.x != 0) & (c0.x != 0) & ((a.x != c0.x) | (a.y != c0.y))) |
+                              ((b.x != 0) & (c1.x != 0) & ((b.x != c1.x) | (b.y != c1.y)));
+                    np = __popcll(__ballot(a.x != 0)) + __popcll(__ballot(b.x != 0));
+                } else if (V.mode == kWaitWide) {
+                    viol = ((a.x & ~c0.x) | (b.x & ~c1.x)) != 0;
+                    changed = (a.x != c0.x) | (a.y != c0.y) | (b.x != c1.x) | (b.y != c1.y);
+                } else {
+                    viol = ((a.x & ~c0.x) | (a.y & ~c0.y) | (b.x & ~c1.x) | (b.y & ~c1.y)) != 0;
+                    changed = (a.x != c0.x) | (a.y != c0.y) | (b.x != c1.x) | (b.y != c1.y);
+                }
+                const uint32_t f = (__ballot(viol) != 0 ? 1u : 0u) | (__ballot(changed) != 0 ? 2u : 0u);
+                if (lane == 0) {
+                    if (f) atomicOr(rec + 2 * (j + k), f);
+                    if (np) atomicAdd(rec + 2 * (j + k) + 1, np);
+                }
+            }
+        }
+    }
+    if constexpr (FUSED) {
+        // the block arriving last writes the answers: every wave's atomics drained, one
+        // agent-scope release ahead of the ticket add, an acquire in the last arriver,
+        // the records read by atomic loads (the ticket is zeroed ahead of the launch)
+        __shared__ uint32_t s_last;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+            s_last = t == gridDim.x - 1 ? 1u : 0u;
+        }
+        __syncthreads();
+        if (s_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            for (uint32_t j = threadIdx.x; j < nws; j += 256) wait_finish(j, vars, ws, rec, nc, met);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_waiter_finish(const WaitVar* vars, const WaitDesc* ws,
+                                                       uint32_t nws, uint32_t* rec, uint32_t* nc,
+                                                       uint8_t* met) {
+    for (uint32_t j = threadIdx.x; j < nws; j += 256) wait_finish(j, vars, ws, rec, nc, met);
 }
 
 struct Guard {
@@ -1734,6 +1899,135 @@ int hydrate(laspj_ctx* ctx, NifState* S, laspj_var* v, bool* ok) {
     return s;
 }
 
+// reply_to_all's test (lasp_core.erl:765-825) for every waiter of n variables in one device
+// pass (S->mu held).  verdict[i]: FALLBACK when variable i's value, or one of its waiters'
+// thresholds, is held on the host; met[i]: one flag per waiter of variable i, in list
+// order (empty when it has no waiters or answered FALLBACK).  No device work when no
+// variable has a waiter to check.
+int recheck_pass(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_var* const* vars,
+                 int32_t* verdict, std::vector<std::vector<uint8_t>>* met) {
+    ++S->stats[0];
+    met->assign(n, {});
+    std::vector<uint32_t> live;
+    uint32_t nws = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        laspj_var* v = vars[i];
+        bool ok = false;
+        if (int s = hydrate(ctx, S, v, &ok)) return s;
+        verdict[i] = ok ? LASPJ_NIF_OK : LASPJ_NIF_FALLBACK;
+        for (size_t k = 0; ok && k < v->waiters.size(); ++k)
+            if (int s = hydrate(ctx, S, v->waiters[k].cells, &ok)) return s;
+        if (!ok) verdict[i] = LASPJ_NIF_FALLBACK;
+    }
+    auto current = [](const laspj_var* v) { return v->resident && v->epoch == v->ns->epoch; };
+    for (uint32_t i = 0; i < n; ++i) {
+        // (a decode above may have started a namespace's dictionary afresh and written the
+        // cells decoded before it out again: such a variable answers FALLBACK this once)
+        laspj_var* v = vars[i];
+        bool ok = verdict[i] == LASPJ_NIF_OK && current(v);
+        for (const Waiter& w : v->waiters) ok = ok && current(w.cells);
+        verdict[i] = ok ? LASPJ_NIF_OK : LASPJ_NIF_FALLBACK;
+        if (!ok) {
+            ++S->stats[6];
+        } else if (!v->waiters.empty()) {
+            live.push_back(i);
+            nws += (uint32_t)v->waiters.size();
+        }
+    }
+    if (live.empty()) return LASPJ_OK;
+    const uint64_t t0 = now_ns();
+    const uint32_t nv = (uint32_t)live.size();
+    // in region (pinned, read by the kernel in place): [WaitVar x nv | WaitDesc x nws];
+    // device words: [ticket, 16 bytes | {flags, np} x nws | nc x nv]; answers: nws bytes
+    const uint64_t i_ws = 32ull * nv, in_bytes = i_ws + 16ull * nws;
+    const uint64_t z_rec = 16, z_nc = z_rec + 8ull * nws, z_bytes = al(z_nc + 4ull * nv, 16);
+    Guard g(ctx);
+    if (int s = grow_dev(ctx, &S->dblk, &S->dblk_bytes, z_bytes)) return s;
+    if (int s = grow_host(ctx, &S->hin, &S->hin_bytes, in_bytes)) return s;
+    if (int s = grow_host(ctx, &S->hout, &S->hout_bytes, nws)) return s;
+    void* hd = nullptr;
+    if (S->hin_dkey != S->hin) {
+        LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hin, 0));
+        S->hin_d = static_cast<uint8_t*>(hd);
+        S->hin_dkey = S->hin;
+    }
+    if (S->hout_dkey != S->hout) {
+        LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hout, 0));
+        S->hout_d = static_cast<uint8_t*>(hd);
+        S->hout_dkey = S->hout;
+    }
+    auto* hv = reinterpret_cast<WaitVar*>(S->hin);
+    auto* hw = reinterpret_cast<WaitDesc*>(static_cast<uint8_t*>(S->hin) + i_ws);
+    uint64_t items = 0;
+    uint32_t w0 = 0;
+    for (uint32_t a = 0; a < nv; ++a) {
+        laspj_var* v = vars[live[a]];
+        const KindState& K = *v->ns;
+        const uint32_t tw = ktw(K);
+        // the value over the namespace's element slots (new(): zeroed cells); a waiter's
+        // cells are re-laid only when the pairs per element changed (the namespace went
+        // wide since): the slots it does not cover are absent
+        if (K.E)
+            if (int s = fit_var(ctx, v, K.E, tw)) return s;
+        const uint32_t nw = (uint32_t)v->waiters.size();
+        WaitVar& d = hv[a];
+        d.cells = v->cells;
+        d.words = v->cells ? (uint32_t)wpr_of(v->kind, v->E, v->tw) : 0;
+        d.mode = v->kind == LASPJ_KIND_GSET ? kWaitGset : tw > 1 ? kWaitWide : kWaitNarrow;
+        d.w0 = w0;
+        d.nw = nw;
+        d.item0 = items;
+        const uint64_t units = (d.words + 1ull) / 2;
+        items += ((units + kWaitTile - 1) / kWaitTile) * ((nw + kWaitChunk - 1) / kWaitChunk);
+        for (uint32_t k = 0; k < nw; ++k) {
+            laspj_var* c = v->waiters[k].cells;
+            if (c->cells && v->kind == LASPJ_KIND_ORSET && c->tw != tw)
+                if (int s = fit_var(ctx, c, K.E, tw)) return s;
+            WaitDesc& e = hw[w0 + k];
+            e.cells = c->cells;
+            e.words = c->cells ? (uint32_t)wpr_of(c->kind, c->E, c->tw) : 0;
+            e.var_strict = a << 1 | (v->waiters[k].strict ? 1u : 0u);
+        }
+        w0 += nw;
+    }
+    uint8_t* dz = static_cast<uint8_t*>(S->dblk);
+    auto* ticket = reinterpret_cast<uint32_t*>(dz);
+    auto* rec = reinterpret_cast<uint32_t*>(dz + z_rec);
+    auto* nc = reinterpret_cast<uint32_t*>(dz + z_nc);
+    const auto* dv = reinterpret_cast<const WaitVar*>(S->hin_d);
+    const auto* dw = reinterpret_cast<const WaitDesc*>(S->hin_d + i_ws);
+    LJ_HIP(ctx, hipMemsetAsync(dz, 0, z_bytes, ctx->stream));
+    const unsigned grid = (unsigned)std::max<uint64_t>(
+        1, std::min<uint64_t>((items + 3) / 4, (uint64_t)ctx->cus * 8));
+    if (ctx->tune_waiter_finish == 2) {
+        hipLaunchKernelGGL(k_waiter_check<true>, dim3(grid), dim3(256), 0, ctx->stream, dv, nv, dw,
+                           nws, items, ticket, rec, nc, S->hout_d);
+        LJ_LAUNCHED(ctx);
+    } else {
+        hipLaunchKernelGGL(k_waiter_check<false>, dim3(grid), dim3(256), 0, ctx->stream, dv, nv,
+                           dw, nws, items, ticket, rec, nc, S->hout_d);
+        LJ_LAUNCHED(ctx);
+        hipLaunchKernelGGL(k_waiter_finish, dim3(1), dim3(256), 0, ctx->stream, dv, dw, nws, rec,
+                           nc, S->hout_d);
+        LJ_LAUNCHED(ctx);
+    }
+    const uint64_t t1 = now_ns();
+    LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t t2 = now_ns();
+    ++S->stats[1];
+    S->stats[8] += t1 - t0;
+    S->stats[9] += t2 - t1;
+    const uint8_t* hout = static_cast<const uint8_t*>(S->hout);
+    w0 = 0;
+    for (uint32_t a = 0; a < nv; ++a) {
+        const uint32_t nw = (uint32_t)vars[live[a]]->waiters.size();
+        (*met)[live[a]].assign(hout + w0, hout + w0 + nw);
+        w0 += nw;
+    }
+    S->stats[10] += now_ns() - t2;
+    return LASPJ_OK;
+}
+
 // a namespace's dictionary and device images dropped (the context still alive)
 void free_ns(KindState& K) {
     free_etf(K);
@@ -2155,10 +2449,26 @@ int laspj_var_create_replica(laspj_var* peer, laspj_var** out) {
 
 int laspj_var_destroy(laspj_var* v) {
     if (!v) return LASPJ_E_INVAL;
+    // its waiters go with it (a context gone first took their cells as it took the
+    // variable's: only the host side is left)
+    auto drop_waiters = [v](laspj::NifState* S) {
+        for (laspj::Waiter& w : v->waiters) {
+            if (w.cells && w.cells->ctx && S) {
+                S->vars.erase(w.cells);
+                w.cells->ns->vars.erase(w.cells);
+                std::lock_guard<std::mutex> lk2(w.cells->ctx->mu);
+                hipSetDevice(w.cells->ctx->device);
+                laspj::release_cells(w.cells->ctx, w.cells);
+            }
+            delete w.cells;
+        }
+        v->waiters.clear();
+    };
     if (v->ctx) {
         laspj::NifState* S = laspj::state(v->ctx);
         if (S) {
             std::lock_guard<std::mutex> lk(S->mu);
+            drop_waiters(S);
             S->vars.erase(v);
             v->ns->vars.erase(v);
             {
@@ -2169,9 +2479,12 @@ int laspj_var_destroy(laspj_var* v) {
             // the namespace's last variable: its device images go too
             if (v->ns.use_count() == 1) laspj::free_ns(*v->ns);
         }
-    } else if (v->ns && v->ns.use_count() == 1 && v->ns->dict) {
-        laspj_dict_destroy(v->ns->dict);         // (its device images went with the context)
-        v->ns->dict = nullptr;
+    } else {
+        drop_waiters(nullptr);
+        if (v->ns && v->ns.use_count() == 1 && v->ns->dict) {
+            laspj_dict_destroy(v->ns->dict);     // (its device images went with the context)
+            v->ns->dict = nullptr;
+        }
     }
     delete v;
     return LASPJ_OK;
@@ -2302,13 +2615,14 @@ int laspj_var_etf_bind(laspj_var* var, const uint8_t* value, uint64_t n, int32_t
     return r.rc;
 }
 
-int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_t* verdict) {
-    laspj::NifState* S = var_state(var);
-    if (!S) return LASPJ_E_INVAL;
-    laspj_ctx* ctx = var->ctx;
-    if ((!value && n) || !verdict) return fail(ctx, LASPJ_E_INVAL, "var_write: null argument");
-    std::lock_guard<std::mutex> lk(S->mu);
-    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_write: unknown variable");
+}  // extern "C"
+
+namespace {
+
+// write/4 (lasp_core.erl:839-844) with S->mu held (laspj_var_etf_write's body; a waiter's
+// threshold is written into its hidden variable the same way)
+int var_write_locked(laspj_ctx* ctx, laspj::NifState* S, laspj_var* var, const uint8_t* value,
+                     uint64_t n, int32_t* verdict) {
     laspj::KindState& K = *var->ns;
     if (!K.dict && laspj::reset_dict(ctx, S, K)) return LASPJ_E_NOMEM;
     // write/4 replaces the value: the old cells (or image) are not read — but a write that
@@ -2370,6 +2684,205 @@ int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_
     var->resident = false;
     var->held = true;
     drop_cells();
+    return LASPJ_OK;
+}
+
+// a waiter's hidden variable leaves the registries and the device (S->mu held when the
+// context is alive)
+void waiter_cells_drop(laspj::NifState* S, laspj_var* c) {
+    if (!c) return;
+    if (c->ctx && S) {
+        S->vars.erase(c);
+        c->ns->vars.erase(c);
+        std::lock_guard<std::mutex> lk(c->ctx->mu);
+        hipSetDevice(c->ctx->device);
+        laspj::release_cells(c->ctx, c);
+    }
+    delete c;
+}
+
+// reply_to_all (lasp_core.erl:765-825) over n variables, S->mu held: the met waiters' ids
+// in list order per variable; removed unless more than cap are met
+int recheck_locked(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_var* const* vars,
+                   uint64_t* ids, uint32_t cap, uint32_t* nmet, int32_t* verdict) {
+    std::vector<std::vector<uint8_t>> met;
+    if (int s = laspj::recheck_pass(ctx, S, n, vars, verdict, &met)) return s;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        nmet[i] = 0;
+        for (uint8_t m : met[i]) nmet[i] += m ? 1u : 0u;
+        total += nmet[i];
+    }
+    if (total > cap || (total && !ids)) return LASPJ_OK;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!nmet[i]) continue;
+        std::vector<laspj::Waiter>& ws = vars[i]->waiters;
+        size_t keep = 0;
+        for (size_t k = 0; k < ws.size(); ++k) {
+            if (met[i][k]) {
+                ids[at++] = ws[k].id;
+                waiter_cells_drop(S, ws[k].cells);
+            } else {
+                if (keep != k) ws[keep] = std::move(ws[k]);
+                ++keep;
+            }
+        }
+        ws.resize(keep);
+    }
+    return LASPJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_t* verdict) {
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if ((!value && n) || !verdict) return fail(ctx, LASPJ_E_INVAL, "var_write: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_write: unknown variable");
+    return var_write_locked(ctx, S, var, value, n, verdict);
+}
+
+int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                   int32_t* met, int32_t* verdict) {
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if ((!threshold && n) || !met || !verdict)
+        return fail(ctx, LASPJ_E_INVAL, "var_wait: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_wait: unknown variable");
+    bool ok = false;
+    if (int s = laspj::hydrate(ctx, S, var, &ok)) return s;
+    *met = 0;
+    *verdict = LASPJ_NIF_FALLBACK;
+    if (!ok) {
+        ++S->stats[6];
+        return LASPJ_OK;
+    }
+    // threshold_met(Type, Value, Threshold) (lasp_lattice.erl:62-75) as
+    // laspj_var_etf_threshold answers it; the pass registers the threshold's terms
+    {
+        laspj::Call c;
+        c.op = laspj::Op::THRESHOLD;
+        c.kind = var->kind;
+        c.strict = strict ? 1 : 0;
+        c.n = c.m = 1;
+        c.p.push_back(threshold);
+        c.len.push_back(n);
+        c.vars.push_back(var);
+        laspj::one_group(c, var->ns.get());
+        std::vector<int32_t> vd;
+        if (int s = laspj::run(ctx, S, c, &vd)) return s;
+        if (vd[0] != LASPJ_NIF_OK) return LASPJ_OK;
+        if (c.res[0]) {
+            *met = 1;
+            *verdict = LASPJ_NIF_OK;
+            return LASPJ_OK;
+        }
+    }
+    // unmet (lasp_core.erl:355-364): appended to waiting_threads, its threshold decoded
+    // into a hidden variable of this namespace (its terms are known now: one more pass)
+    laspj_var* cells = nullptr;
+    if (int s = var_new(ctx, S, var->kind, var->ns, &cells)) return s;
+    int32_t wv = LASPJ_NIF_FALLBACK;
+    int s = var_write_locked(ctx, S, cells, threshold, n, &wv);
+    if (s == LASPJ_OK && wv == LASPJ_NIF_OK) {
+        try {
+            laspj::Waiter w;
+            w.id = id;
+            w.strict = strict ? 1 : 0;
+            w.image.assign(threshold, threshold + n);
+            w.cells = cells;
+            var->waiters.push_back(std::move(w));
+            *verdict = LASPJ_NIF_OK;
+            return LASPJ_OK;
+        } catch (const std::bad_alloc&) {
+            s = fail(ctx, LASPJ_E_NOMEM, "var_wait: host allocation");
+        }
+    }
+    waiter_cells_drop(S, cells);
+    return s;
+}
+
+int laspj_var_recheck(laspj_var* var, uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                      uint32_t* nwaiting, int32_t* verdict) {
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if ((!ids && cap) || !nmet || !nwaiting || !verdict)
+        return fail(ctx, LASPJ_E_INVAL, "var_recheck: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_recheck: unknown variable");
+    *nmet = 0;
+    const int s = recheck_locked(ctx, S, 1, &var, ids, cap, nmet, verdict);
+    *nwaiting = (uint32_t)var->waiters.size();
+    return s;
+}
+
+int laspj_var_recheck_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars, uint64_t* ids,
+                           uint32_t cap, uint32_t* nmet, int32_t* verdict) {
+    if (!ctx) return LASPJ_E_INVAL;
+    if (!n) return LASPJ_OK;
+    if (!vars || (!ids && cap) || !nmet || !verdict)
+        return fail(ctx, LASPJ_E_INVAL, "var_recheck: null array");
+    laspj::NifState* S = laspj::state(ctx);
+    if (!S) return fail(ctx, LASPJ_E_NOMEM, "nif: state allocation");
+    std::lock_guard<std::mutex> lk(S->mu);
+    std::unordered_set<laspj_var*> seen;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!vars[i] || vars[i]->ctx != ctx || !S->vars.count(vars[i]))
+            return fail(ctx, LASPJ_E_INVAL, "var_recheck: variable %u is not this context's", i);
+        if (!seen.insert(vars[i]).second)
+            return fail(ctx, LASPJ_E_INVAL, "var_recheck: variable %u named twice", i);
+    }
+    return recheck_locked(ctx, S, n, vars, ids, cap, nmet, verdict);
+}
+
+int laspj_var_wait_cancel(laspj_var* var, uint64_t id, int32_t* found) {
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if (!found) return fail(ctx, LASPJ_E_INVAL, "var_wait_cancel: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_wait_cancel: unknown variable");
+    *found = 0;
+    for (size_t k = 0; k < var->waiters.size(); ++k)
+        if (var->waiters[k].id == id) {
+            waiter_cells_drop(S, var->waiters[k].cells);
+            var->waiters.erase(var->waiters.begin() + (ptrdiff_t)k);
+            *found = 1;
+            break;
+        }
+    return LASPJ_OK;
+}
+
+int laspj_var_waiter_count(const laspj_var* var, uint32_t* n) {
+    laspj::NifState* S = var_state(const_cast<laspj_var*>(var));
+    if (!S || !n) return LASPJ_E_INVAL;
+    std::lock_guard<std::mutex> lk(S->mu);
+    *n = (uint32_t)var->waiters.size();
+    return LASPJ_OK;
+}
+
+int laspj_var_waiter_at(laspj_var* var, uint32_t k, uint64_t* id, int32_t* strict,
+                        const uint8_t** threshold, uint64_t* n) {
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if (!id || !strict || !threshold || !n)
+        return fail(ctx, LASPJ_E_INVAL, "var_waiter_at: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (k >= var->waiters.size()) return fail(ctx, LASPJ_E_RANGE, "var_waiter_at: no waiter %u", k);
+    const laspj::Waiter& w = var->waiters[k];
+    *id = w.id;
+    *strict = w.strict;
+    *threshold = w.image.data();
+    *n = w.image.size();
     return LASPJ_OK;
 }
 

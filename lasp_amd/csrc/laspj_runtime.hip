@@ -376,6 +376,11 @@ int laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value) {
                 return fail(ctx, LASPJ_E_INVAL, "tuning: list chunk 0 or 64 .. 2^20");
             ctx->tune_list_chunk = value;
             return LASPJ_OK;
+        case LASPJ_TUNE_WAITER_FINISH:
+            if (value < 0 || value > 2)
+                return fail(ctx, LASPJ_E_INVAL, "tuning: waiter finish 0 .. 2");
+            ctx->tune_waiter_finish = value;
+            return LASPJ_OK;
 
         default:
             return fail(ctx, LASPJ_E_INVAL, "tuning: unknown knob %d", knob);

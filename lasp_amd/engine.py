@@ -205,6 +205,27 @@ class Context:
         check(self.L.laspj_var_etf_bind_many(self.h, n, vs, pv, nv, st, verd), self.h)
         return [(int(verd[k]), int(st[k])) for k in range(n)]
 
+    def var_recheck_many(self, vars, cap: int = 64):
+        """laspj_var_recheck_many over NifVars: [(verdict, [ids met])] per variable."""
+        n = len(vars)
+        if n == 0:
+            return []
+        vs = (C.c_void_p * n)(*[v.h.value for v in vars])
+        while True:
+            ids = (C.c_uint64 * max(cap, 1))()
+            nmet = (C.c_uint32 * n)()
+            verd = (C.c_int32 * n)()
+            check(self.L.laspj_var_recheck_many(self.h, n, vs, ids, cap, nmet, verd), self.h)
+            total = sum(int(x) for x in nmet)
+            if total <= cap:
+                break
+            cap = total
+        out, at = [], 0
+        for k in range(n):
+            out.append((int(verd[k]), [int(x) for x in ids[at:at + nmet[k]]]))
+            at += nmet[k]
+        return out
+
     def nif_stats(self) -> dict:
         out = (C.c_uint64 * _lib.NIF_STATS)()
         check(self.L.laspj_nif_stats(self.h, out, _lib.NIF_STATS), self.h)
@@ -320,6 +341,44 @@ class NifVar:
         r = C.c_int32()
         check(self.L.laspj_var_resident(self.h, C.byref(r)), self.ctx.h)
         return bool(r.value)
+
+    def wait(self, img: bytes, strict: bool = False, id: int = 0):
+        """read/6 (laspj_var_wait): (verdict, met) — an unmet threshold is registered as a
+        waiter {id, strict, img}; met is None on NIF_FALLBACK."""
+        met, verd = C.c_int32(), C.c_int32()
+        img = bytes(img)
+        check(self.L.laspj_var_wait(self.h, img, len(img), int(strict), id, C.byref(met),
+                                    C.byref(verd)), self.ctx.h)
+        return int(verd.value), (bool(met.value) if verd.value == 0 else None)
+
+    def recheck(self, cap: int = 16):
+        """write/4's reply_to_all (laspj_var_recheck): (verdict, [ids met, in registration
+        order], waiters left); asks again with more room when more than cap are met."""
+        while True:
+            ids = (C.c_uint64 * max(cap, 1))()
+            nmet, left, verd = C.c_uint32(), C.c_uint32(), C.c_int32()
+            check(self.L.laspj_var_recheck(self.h, ids, cap, C.byref(nmet), C.byref(left),
+                                           C.byref(verd)), self.ctx.h)
+            if nmet.value <= cap:
+                return int(verd.value), [int(x) for x in ids[:nmet.value]], int(left.value)
+            cap = nmet.value
+
+    def cancel(self, id: int) -> bool:
+        found = C.c_int32()
+        check(self.L.laspj_var_wait_cancel(self.h, id, C.byref(found)), self.ctx.h)
+        return bool(found.value)
+
+    def waiters(self):
+        """[(id, strict, threshold image)] in list order."""
+        n = C.c_uint32()
+        check(self.L.laspj_var_waiter_count(self.h, C.byref(n)), self.ctx.h)
+        out = []
+        for k in range(n.value):
+            wid, strict, p, ln = C.c_uint64(), C.c_int32(), C.c_void_p(), C.c_uint64()
+            check(self.L.laspj_var_waiter_at(self.h, k, C.byref(wid), C.byref(strict),
+                                             C.byref(p), C.byref(ln)), self.ctx.h)
+            out.append((int(wid.value), bool(strict.value), C.string_at(p, ln.value)))
+        return out
 
 
 def device_count() -> int:
