@@ -11,7 +11,13 @@
 extern "C" {
 #endif
 
-#define LASPJ_TUNE_STREAM_GRID   1   /* workgroups for grid-stride streaming kernels    */
+#define LASPJ_TUNE_STREAM_GRID   1   /* workgroups for grid-stride streaming kernels; when
+                                        set it is also the grid cap of the segment / item
+                                        kernels (reduce segments, fragment, value, stats,
+                                        equal, inflation, G-Counter sums / threshold /
+                                        inflation / increment, filter, fused gather +
+                                        inflation), so tests reach their strides with few
+                                        items; 0 = each launch's own default            */
 #define LASPJ_TUNE_STREAM_UNROLL 2   /* 16-B cells per lane per iteration: 1,2,4,8      */
 #define LASPJ_TUNE_STREAM_NT     3   /* 1 = non-temporal loads/stores, 0 = default      */
 #define LASPJ_TUNE_ETF_KERNEL    4   /* OR-Set payload writer: 0 = record kernel when the

@@ -61,6 +61,13 @@ StreamTune stream_tune(const laspj_ctx* ctx, uint64_t n16) {
     return t;
 }
 
+// grid cap of the segment / item kernels (one block or wave per item, striding when the
+// items outnumber the cap): the stream grid knob when set, so a test can make a few
+// items take several strides; the launch's own default otherwise
+static uint64_t grid_cap(const laspj_ctx* ctx, uint64_t dflt) {
+    return ctx->tune_grid > 0 ? (uint64_t)ctx->tune_grid : dflt;
+}
+
 // ------------------------------------------------------------------ join: d = a | b
 
 template <int U, bool NT>
@@ -321,7 +328,7 @@ hipError_t launch_reduce_or(laspj_ctx* ctx, uint64_t* dst, const uint64_t* src,
     bool vec2 = (wr % 2) == 0;
     uint64_t per = vec2 ? wr / 2 : wr;
     uint32_t ns = (uint32_t)((per + kRSeg - 1) / kRSeg);
-    uint64_t items = groups * ns, cap = (uint64_t)ctx->cus * 32;
+    uint64_t items = groups * ns, cap = grid_cap(ctx, (uint64_t)ctx->cus * 32);
     unsigned g = (unsigned)(items < cap ? (items ? items : 1) : cap);
     auto* d2 = reinterpret_cast<u64x2*>(dst);
     auto* s2 = reinterpret_cast<const u64x2*>(src);
@@ -742,7 +749,8 @@ __global__ __launch_bounds__(kBlock) void k_orset_context(u64x2* d, const u64x2*
 
 hipError_t launch_orset_fragment(laspj_ctx* ctx, const laspj_batch* b, uint32_t e, void* out) {
     uint64_t g = (b->replicas * b->tok_words + kBlock - 1) / kBlock;
-    if (g > (uint64_t)ctx->cus * 16) g = (uint64_t)ctx->cus * 16;
+    const uint64_t cap = grid_cap(ctx, (uint64_t)ctx->cus * 16);
+    if (g > cap) g = cap;
     hipLaunchKernelGGL(k_orset_fragment, dim3((unsigned)(g ? g : 1)), dim3(kBlock), 0, ctx->stream,
                        reinterpret_cast<const u64x2*>(b->dev), reinterpret_cast<u64x2*>(out),
                        b->replicas, b->elements, e, b->tok_words);
@@ -827,7 +835,7 @@ hipError_t launch_orset_value(laspj_ctx* ctx, const laspj_batch* b, uint64_t* ou
     const uint32_t sg = (uint32_t)seg_for(b->replicas, b->elements, kVSeg);
     uint32_t ns = (b->elements + sg - 1) / sg;
     uint64_t items = b->replicas * ns;
-    uint64_t blocks = (items + 3) / 4, cap = (uint64_t)ctx->cus * 16;
+    uint64_t blocks = (items + 3) / 4, cap = grid_cap(ctx, (uint64_t)ctx->cus * 16);
     int grid = (int)(blocks < cap ? (blocks ? blocks : 1) : cap);
     auto* cells = reinterpret_cast<const u64x2*>(b->dev);
     // words in flight per lane: 4 (default) or the stream unroll knob when it is 8
@@ -965,7 +973,7 @@ static uint32_t nseg_of(uint64_t n, uint64_t seg) { return (uint32_t)((n + seg -
 
 static int seg_grid(const laspj_ctx* ctx, uint64_t items) {
     uint64_t blocks = (items + 3) / 4;
-    uint64_t cap = (uint64_t)ctx->cus * 16;
+    uint64_t cap = grid_cap(ctx, (uint64_t)ctx->cus * 16);
     if (blocks > cap) blocks = cap;
     return blocks ? (int)blocks : 1;
 }
@@ -1323,7 +1331,7 @@ hipError_t launch_gather_inflation(laspj_ctx* ctx, laspj_batch* dst, const laspj
     const uint64_t items = (dst->replicas + kFRun - 1) / kFRun * ns;
     // one (run, segment) item per block, no grid stride: 21.5 ms against 22.5 ms with 32
     // blocks per CU striding (profiles/r02_sweep_c4_grid.log)
-    const uint64_t cap = ctx->tune_grid > 0 ? (uint64_t)ctx->tune_grid : (1ull << 30);
+    const uint64_t cap = grid_cap(ctx, 1ull << 30);
     const uint64_t g = items < cap ? items : cap;
     const bool bc = prev->replicas == 1 && dst->replicas != 1;
     u64* part = nullptr;
@@ -1681,7 +1689,8 @@ __global__ __launch_bounds__(kBlock) void k_gcounter_incr(u64* c, uint64_t W,
 hipError_t launch_gcounter_incr(laspj_ctx* ctx, laspj_batch* b, const laspj_incr* incs,
                                 uint64_t n) {
     uint64_t g = (n + kBlock - 1) / kBlock;
-    if (g > (uint64_t)ctx->cus * 16) g = (uint64_t)ctx->cus * 16;
+    const uint64_t cap = grid_cap(ctx, (uint64_t)ctx->cus * 16);
+    if (g > cap) g = cap;
     hipLaunchKernelGGL(k_gcounter_incr, dim3((unsigned)(g ? g : 1)), dim3(kBlock), 0, ctx->stream,
                        (u64*)b->dev, b->words_per_replica, incs, n);
     return hipGetLastError();
@@ -1809,7 +1818,7 @@ __global__ __launch_bounds__(kBlock) void k_orset_filter(u64x2* d, const u64x2* 
 }
 
 static int seg_blocks(const laspj_ctx* ctx, uint64_t items) {
-    uint64_t cap = (uint64_t)ctx->cus * 32;
+    uint64_t cap = grid_cap(ctx, (uint64_t)ctx->cus * 32);
     return (int)(items < cap ? (items ? items : 1) : cap);
 }
 

@@ -209,6 +209,7 @@ def test_reduce_chunks_every_kind(ctx, nchunks):
         w = src.words_per_replica
         if op == "max":       # small counts so chunks collide, some equal
             hs = rng.integers(0, 5, size=(nchunks * n, w), dtype=np.uint64)
+            hs[::7] = np.uint64(2**64 - 1) - hs[::7]  # counts above 2^63: unsigned max
         else:
             hs = rng.integers(0, 2**63, size=(nchunks * n, w), dtype=np.uint64) * np.uint64(2) \
                 + rng.integers(0, 2, size=(nchunks * n, w), dtype=np.uint64)
@@ -246,6 +247,7 @@ def test_join_n_every_kind(ctx, n):
         for b in srcs:
             if op == "max":
                 h = rng.integers(0, 5, size=(R_, w), dtype=np.uint64)
+                h[len(hs)::7] = np.uint64(2**64 - 1) - h[len(hs)::7]  # above 2^63: unsigned
             else:
                 h = rng.integers(0, 2**63, size=(R_, w), dtype=np.uint64) * np.uint64(2) \
                     + rng.integers(0, 2, size=(R_, w), dtype=np.uint64)
@@ -293,6 +295,8 @@ def test_batch_join_gcounter_is_max(ctx):
     a, b, c, d = (ctx.gcounter_batch(33, 9) for _ in range(4))
     ha = rng.integers(0, 6, size=(33, 9), dtype=np.uint64)
     hb = rng.integers(0, 6, size=(33, 9), dtype=np.uint64)
+    ha[::7] = np.uint64(2**64 - 1) - ha[::7]          # counts above 2^63: unsigned max
+    hb[3::7] = np.uint64(2**64 - 1) - hb[3::7]
     a.upload(ha)
     b.upload(hb)
     L = ctx.L
