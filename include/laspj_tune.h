@@ -54,13 +54,13 @@ extern "C" {
                                         hold <= 8 token slots, and long payloads split
                                         between waves when there are few of them,
                                         1 = serial record scan, 2 = batched records
-                                        without element batches, 3 = never split,
-                                        4 = always split (256-byte segments),
-                                        5 = always split (sized segments), 6 = element
+                                        without element batches,
+                                        4 = always split (256-byte segments), 6 = element
                                         batches walked by the scalar unit (the lanes
-                                        find element starts by default), 7 = no element
+                                        find element starts by default; always split,
+                                        sized segments), 7 = no element
                                         batches for many-token dictionaries (one element
-                                        at a time), 8 = the same as 0, 10 = as 0, with
+                                        at a time), 10 = as 0, with
                                         segment mode's redo pass as a launch of its own
                                         (by default the chain check's wave decodes a
                                         payload that failed it again itself).
@@ -93,10 +93,6 @@ extern "C" {
 #define LASPJ_TUNE_LIST_CHUNK   15   /* rows per chunk of the list merges' chunked walk
                                         (0 = default: 1024, or more to keep <= 1024
                                         chunks; 64 .. 2^20)                             */
-#define LASPJ_TUNE_WAITER_FINISH 16   /* laspj_var_recheck's met flags: 0 = default (the
-                                        one-block finish launch behind the check), 1 = that
-                                        finish launch, 2 = written by the check's
-                                        last-arriving block (ticket counter); for A/B   */
 int         laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value);
 
 #ifdef __cplusplus

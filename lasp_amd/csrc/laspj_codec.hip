@@ -4947,20 +4947,20 @@ void etf_read_plan(const laspj_ctx* ctx, const laspj_etf_dict* d, uint64_t R, co
     // (fewer than 8 per CU) and they are long: segments of S bytes, S sized for ~48 waves
     // per CU (6 resident per SIMD, the rest queued behind them for balance), at least
     // 2 KiB.  Knob 4 splits every payload longer than 256 bytes into 256-byte segments
-    // (what the tests use to stress the chain), 5 always splits with the sized S.
+    // (what the tests use to stress the chain); 6 splits whatever the count, with the sized S.
     plan->S = plan->nseg = 0;
     plan->segbase.clear();
-    const bool batched = d->rd_desc && ctx->tune_etf_read != 1;
-    if (!(batched && d->rd_htab && ctx->tune_etf_read != 3)) return;
+    const int64_t form = ctx->tune_etf_read;
+    const bool batched = d->rd_desc && form != 1;
+    if (!(batched && d->rd_htab)) return;
     const uint64_t bytes_in = off[R] - off[0];
     const uint64_t want = (uint64_t)ctx->cus * 48;
     uint64_t longest = 0;
     for (uint64_t i = 0; i < R; ++i) longest = std::max<uint64_t>(longest, off[i + 1] - off[i]);
     uint64_t S = std::max<uint64_t>(2048, ((bytes_in / want) + 255) & ~255ull);
-    if (ctx->tune_etf_read == 4) S = 256;
+    if (form == 4) S = 256;
     if (ctx->tune_etf_seg) S = (uint64_t)ctx->tune_etf_seg;
-    const bool split = (ctx->tune_etf_read >= 4 && ctx->tune_etf_read <= 6) ||
-                       ctx->tune_etf_seg || R < (uint64_t)ctx->cus * 8;
+    const bool split = form == 4 || form == 6 || ctx->tune_etf_seg || R < (uint64_t)ctx->cus * 8;
     if (!(longest < (1ull << 31) && split && longest > S)) return;
     uint64_t acc = 0;
     plan->segbase.resize(R + 1);
@@ -4986,18 +4986,20 @@ int etf_read_enqueue(laspj_ctx* ctx, laspj_batch* b, const laspj_etf_dict* d, in
     if (clear)
         LJ_HIP(ctx, hipMemsetAsync(b->dev, 0, b->replicas * b->words_per_replica * 8ull,
                                    ctx->stream));
-    const bool batched = d->rd_desc && ctx->tune_etf_read != 1;
-    auto kread = small_dict(d) && (ctx->tune_etf_read == 0 || ctx->tune_etf_read == 6 ||
-                                              ctx->tune_etf_read >= 8)
-                     ? k_orset_etf_read<true> : k_orset_etf_read<false>;
+    const int64_t form = ctx->tune_etf_read;
+    const bool batched = d->rd_desc && form != 1;
+    // whole elements per lane when they hold <= 8 token slots (the default, and the forms
+    // that only change something else: 6, and 10 and up); 1, 2, 4 and 7 walk records
+    const bool elem_batches = small_dict(d) && (form == 0 || form == 6 || form >= 10);
+    auto kread = elem_batches ? k_orset_etf_read<true> : k_orset_etf_read<false>;
     ReadTabs tabs{static_cast<const uint4*>(d->rd_desc), d->rd_hdr, d->rd_tb, d->rd_ros};
     if (nt && nt->out && d->bin_tokens) tabs.nt = *nt;
     // the header hash (segment search; element batches without the scalar walk — knob 6
     // keeps the walking element batches)
     const HdrHash hh{d->rd_htab, d->rd_hmask, d->rd_hlens};
     // (knob 7: many-token dictionaries decode one element at a time)
-    const HdrHash hh_small{ctx->tune_etf_read == 6 ? nullptr : d->rd_htab, d->rd_hmask,
-                           d->rd_hlens, ctx->tune_etf_read == 7 ? 0u : 1u};
+    const HdrHash hh_small{form == 6 ? nullptr : d->rd_htab, d->rd_hmask, d->rd_hlens,
+                           form == 7 ? 0u : 1u};
     if (plan.nseg) {
         const uint64_t nseg = plan.nseg;
         auto al = [](uint64_t x) { return (x + 255ull) & ~255ull; };
@@ -5016,7 +5018,7 @@ int etf_read_enqueue(laspj_ctx* ctx, laspj_batch* b, const laspj_etf_dict* d, in
         SegRes* dres = deferred ? static_cast<SegRes*>(defer->res)
                                 : reinterpret_cast<SegRes*>(sc + o_res);
         const uint64_t sblocks = (nseg + 3) / 4, scap = (uint64_t)ctx->cus * 64;
-        const bool small = small_dict(d) && ctx->tune_etf_read != 2;
+        const bool small = small_dict(d) && form != 2;
         hipLaunchKernelGGL(small ? k_orset_etf_read_seg<true> : k_orset_etf_read_seg<false>,
                            dim3((unsigned)std::min(sblocks, scap)), dim3(kBlock), 0, ctx->stream,
                            payload, (u64)payload_bytes, offs, R, b->elements, view(d), tabs, tag,
@@ -5035,16 +5037,13 @@ int etf_read_enqueue(laspj_ctx* ctx, laspj_batch* b, const laspj_etf_dict* d, in
         }
         // the chain check, whose wave decodes a failed replica again itself (knob 10: the
         // redo list and a launch of the wave decoder over it, as before)
-        const bool inline_redo = ctx->tune_etf_read != 10;
+        const bool inline_redo = form != 10;
         uint32_t* redo = redo_zeroed;
         if (!redo && !inline_redo) {
             redo = reinterpret_cast<uint32_t*>(sc + o_redo);
             LJ_HIP(ctx, hipMemsetAsync(redo, 0, 4, ctx->stream));
         }
-        const bool csmall = small_dict(d) &&
-                            (ctx->tune_etf_read == 0 || ctx->tune_etf_read == 6 ||
-                             ctx->tune_etf_read >= 8);
-        hipLaunchKernelGGL(csmall ? k_etf_read_chain<true> : k_etf_read_chain<false>,
+        hipLaunchKernelGGL(elem_batches ? k_etf_read_chain<true> : k_etf_read_chain<false>,
                            dim3((unsigned)std::min<uint64_t>(R, (uint64_t)ctx->cus * 32)), dim3(64), 0,
                            ctx->stream, payload, (u64)payload_bytes, offs, R, dsegbase,
                            (uint32_t)plan.S, dres, status, redo, b->elements, view(d), tabs,

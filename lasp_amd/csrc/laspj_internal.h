@@ -39,7 +39,6 @@ struct laspj_ctx {
     int64_t tune_list_walk = 0;
     int64_t tune_nif_passes = 0;     // NIF device passes per call (0: the default)
     int64_t tune_list_chunk = 0;     // rows per chunk of the chunked list walk (0: default)
-    int64_t tune_waiter_finish = 0;  // the waiter re-check's finish (0: default)
     // device scratch for apply_ops (grown on demand)
     void* scratch = nullptr;
     uint64_t scratch_bytes = 0;

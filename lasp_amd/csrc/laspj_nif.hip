@@ -143,6 +143,32 @@ struct BindReq {
     bool done = false, lead = false;
 };
 
+// the counters of laspj_nif_stats, by the indices include/laspj.h documents
+enum NifStat : uint32_t {
+    ST_CALLS,           // [0] calls
+    ST_PASSES,          // [1] device passes
+    ST_REGISTRATIONS,   // [2] dictionary registrations
+    ST_RESETS,          // [3] dictionary resets
+    ST_REBUILDS,        // [4] device image rebuilds
+    ST_HOST_ENCODED,    // [5] host-encoded passes
+    ST_FALLBACKS,       // [6] FALLBACK verdicts
+    ST_DICT_ELEMENTS,   // [7] dictionary elements (computed when read, never counted)
+    ST_NS_ENQUEUE,      // [8] host ns staging + enqueueing
+    ST_NS_WAIT,         // [9] host ns waiting for the device
+    ST_NS_ANSWERS,      // [10] host ns reading the answers
+    ST_NS_COPY,         // [11] the part of [8] copying operands into pinned memory
+    ST_NS_REGISTER,     // [12] host ns registering operands' terms
+    ST_NS_IMAGES,       // [13] host ns rebuilding or patching the device images
+    ST_PATCHES,         // [14] device image patches
+    ST_CHAIN_REDOS,     // [15] passes run again for a chain only a serial decode judges
+    ST_SPILLED,         // [16] variables written out by a dictionary reset
+    ST_HYDRATED,        // [17] variables decoded back onto the device
+    ST_NEW_TOKENS,      // [18] tokens taken by a decoder, registered after the pass
+    ST_WIDENED,         // [19] namespaces widened
+    ST_COUNT
+};
+static_assert(ST_COUNT == LASPJ_NIF_STATS, "NifStat names every laspj_nif_stats entry");
+
 struct NifState {
     std::mutex mu;                  // one call at a time (ctx->mu is held per device phase)
     // single binds queued for the next group-commit pass, and whether a caller leads one
@@ -156,14 +182,15 @@ struct NifState {
     std::vector<PinSlot> pins;      // free waiters' staging blocks (qmu)
     uint32_t pins_live = 0;         // blocks allocated (qmu)
     KindState ks[2];                // the image calls' dictionaries: [0] OR-Set, [1] G-Set
-    // device: [in region: offsets | segment table | zeroed words | variable cell pointers
-    // | payloads or cells][segment results][variable calls' statuses]; cells: the batches
+    // the device block and the cell area of a pass, laid out by PassLayout (the waiter
+    // re-check keeps its records at the head of dblk: recheck_pass)
     void* dblk = nullptr;
     uint64_t dblk_bytes = 0;
     void* dcells = nullptr;
     uint64_t dcells_bytes = 0;
     // pinned host staging, coherent (kernels pull the operands from one and write the
-    // answers into the other), and the device addresses of both
+    // answers into the other: PassLayout's in and out regions), and the device addresses
+    // of both (fit_staging)
     void* hin = nullptr;
     uint64_t hin_bytes = 0;
     void* hout = nullptr;
@@ -408,8 +435,7 @@ __global__ void __launch_bounds__(256) k_var_union(uint64_t* out, const uint64_t
 // Records (zeroed ahead of the launch): per waiter {flags: 1 violation, 2 changed; np},
 // per variable nc (a property of the value alone: counted by the first chunk's waves);
 // device-scope atomics, one per wave and nonzero result.  The met flags are written to
-// the pinned answer area by a one-block finish launch, or (FUSED) by the block whose
-// ticket shows it arrived last.
+// the pinned answer area by a one-block finish launch behind the check.
 constexpr uint32_t kWaitTile = 128;     // units per wave item: two per lane
 constexpr uint32_t kWaitChunk = 16;     // waiters per wave item
 constexpr uint32_t kWaitNarrow = 0, kWaitWide = 1, kWaitGset = 2;
@@ -447,11 +473,9 @@ __device__ __forceinline__ void wait_finish(uint32_t j, const WaitVar* vars, con
     met[j] = res ? 1 : 0;
 }
 
-template <bool FUSED>
 __global__ void __launch_bounds__(256) k_waiter_check(const WaitVar* vars, uint32_t nv,
-                                                      const WaitDesc* ws, uint32_t nws,
-                                                      uint64_t items, uint32_t* ticket,
-                                                      uint32_t* rec, uint32_t* nc, uint8_t* met) {
+                                                      const WaitDesc* ws, uint64_t items,
+                                                      uint32_t* rec, uint32_t* nc) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t nwaves = (uint64_t)gridDim.x * 4;
     for (uint64_t s = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6; s < items; s += nwaves) {
@@ -514,26 +538,6 @@ __global__ void __launch_bounds__(256) k_waiter_check(const WaitVar* vars, uint3
                     if (np) atomicAdd(rec + 2 * (j + k) + 1, np);
                 }
             }
-        }
-    }
-    if constexpr (FUSED) {
-        // the block arriving last writes the answers: every wave's atomics drained, one
-        // agent-scope release ahead of the ticket add, an acquire in the last arriver,
-        // the records read by atomic loads (the ticket is zeroed ahead of the launch)
-        __shared__ uint32_t s_last;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-            s_last = t == gridDim.x - 1 ? 1u : 0u;
-        }
-        __syncthreads();
-        if (s_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            for (uint32_t j = threadIdx.x; j < nws; j += 256) wait_finish(j, vars, ws, rec, nc, met);
         }
     }
 }
@@ -642,6 +646,13 @@ struct Call {
     bool write_only = false;
 };
 
+// the group payload i belongs to
+size_t group_of(const Call& c, uint32_t i) {
+    size_t g = 0;
+    while (g + 1 < c.groups.size() && i >= c.groups[g].p1) ++g;
+    return g;
+}
+
 KindState& kstate(NifState* S, int32_t kind) {
     return S->ks[kind == LASPJ_KIND_GSET ? 1 : 0];
 }
@@ -744,8 +755,8 @@ int rebuild_wide(laspj_ctx* ctx, NifState* S, KindState& K) {
         std::vector<uint32_t> gone;
         dict_take_dirty(K.dict, &gone);
     }
-    ++S->stats[4];
-    S->stats[13] += now_ns() - t0;
+    ++S->stats[ST_REBUILDS];
+    S->stats[ST_NS_IMAGES] += now_ns() - t0;
     return LASPJ_OK;
 }
 
@@ -759,7 +770,7 @@ bool go_wide(NifState* S, KindState& K) {
     if (!dict_set_tok_cap(K.dict, kWideTokens, kWideTokenLen)) return false;
     K.wide = true;
     K.stale = true;
-    ++S->stats[19];
+    ++S->stats[ST_WIDENED];
     return true;
 }
 
@@ -812,8 +823,8 @@ int rebuild_etf(laspj_ctx* ctx, NifState* S, KindState& K) {
     }
     K.built_cnt.resize(n);
     for (uint32_t e = 0; e < n; ++e) K.built_cnt[e] = toks ? dict_token_count(K.dict, e) : 0;
-    ++S->stats[4];
-    S->stats[13] += now_ns() - t0;
+    ++S->stats[ST_REBUILDS];
+    S->stats[ST_NS_IMAGES] += now_ns() - t0;
     return LASPJ_OK;
 }
 
@@ -836,8 +847,8 @@ bool patch_etf(laspj_ctx* ctx, NifState* S, KindState& K) {
         return false;
     for (uint32_t e : dirty) K.built_cnt[e] = dict_token_count(K.dict, e);
     K.stale = false;
-    ++S->stats[14];
-    S->stats[13] += now_ns() - t0;
+    ++S->stats[ST_PATCHES];
+    S->stats[ST_NS_IMAGES] += now_ns() - t0;
     return true;
 }
 
@@ -880,564 +891,741 @@ int fit_var(laspj_ctx* ctx, laspj_var* v, uint32_t E, uint32_t tw = 1) {
     return LASPJ_OK;
 }
 
-// One device pass: stage, pull, decode (or upload host-encoded cells), answer, one
-// synchronisation.  Fills c.st / c.res / c.ooff / c.obase.
+// device_pass's answer when the writer found the answer area short: nothing was written, the
+// area has been grown (S->ocap) and run() takes the pass again
+constexpr int kPassAgain = -1000;
 
-int device_pass(laspj_ctx* ctx, NifState* S, Call& c) {
-    const uint64_t t0 = now_ns();
-    uint64_t t_copy = 0;
+// What one device pass does: decided once, from the call and its dictionaries' state.
+struct PassPlan {
+    bool orset = false;
+    bool wide = false;              // (single-group ops: answers by the wide codec)
+    bool dec = false;               // the device decodes the operands (else the host encodes cells)
+    bool var_op = false;            // BIND / WRITE: a kernel joins into resident cells
+    bool var_in = false;            // the call reads resident cells
+    bool any_wide = false;
+    bool multi = false;             // several namespaces' payloads in one decode launch
+    bool has_payload_out = false;   // the answer is an image (MERGE / VALUE / READ / VVALUE)
+    bool defer = false;             // the chain check rides on the answer's launch (ChainJob)
+    bool nt_merge = false, nt_on = false;   // the decoder takes unseen tokens (NewTok)
+    bool gathered = false;          // payloads staged by group-commit waiters: k_nif_gather
+    std::vector<unsigned long long> hoffs;  // m + 1: the payloads laid end to end
+    uint64_t pay = 0;                       // their bytes
+    std::vector<EtfGroup> eg;               // per group (cells: PassMem's copy)
+    std::vector<EtfReadPlan> plans;         // one over every payload (multi), else per group
+};
+
+PassPlan plan_pass(const laspj_ctx* ctx, const Call& c) {
+    PassPlan P;
     const uint32_t m = c.m, n = c.n;
     const size_t G = c.groups.size();
     // single-group ops (every op but BIND / WRITE) answer over group 0's dictionary
-    KindState& K = *c.groups[0].K;
-    const uint32_t E = K.E, TW = ktw(K);
-    const bool orset = c.kind == LASPJ_KIND_ORSET;
-    const bool wide = orset && K.wide;            // (single-group ops: answers by the wide codec)
-    bool dec = m != 0;
+    const KindState& K = *c.groups[0].K;
+    const uint32_t E = K.E;
+    P.orset = c.kind == LASPJ_KIND_ORSET;
+    P.wide = P.orset && K.wide;
+    P.dec = m != 0;
     // (a wide namespace's operands are encoded by the host dictionary: dict_encode_cells)
     for (const Group& g : c.groups)
-        if (orset && g.p1 > g.p0 && (g.K->wide || !etf_dict_decodable(g.K->etf))) dec = false;
-    const bool var_op = c.op == Op::BIND || c.op == Op::WRITE;
-    const bool var_in = var_op || c.op == Op::THRESHOLD || c.op == Op::READ || c.op == Op::VVALUE;
-    std::vector<unsigned long long> hoffs(m + 1ull, 0);
-    for (uint32_t i = 0; i < m; ++i) hoffs[i + 1] = hoffs[i] + c.len[i];
-    const uint64_t pay = hoffs[m];
-    // per group: its operand cells (words into the cell area: its payloads' replicas at its
-    // own width)
-    std::vector<uint64_t> gseg(G, 0), gcell(G, 0);
-    std::vector<EtfGroup> eg(G);
-    uint64_t seg_area = 0, in_words = 0;
+        if (P.orset && g.p1 > g.p0 && (g.K->wide || !etf_dict_decodable(g.K->etf))) P.dec = false;
+    P.var_op = c.op == Op::BIND || c.op == Op::WRITE;
+    P.var_in = P.var_op || c.op == Op::THRESHOLD || c.op == Op::READ || c.op == Op::VVALUE;
+    P.hoffs.assign(m + 1ull, 0);
+    for (uint32_t i = 0; i < m; ++i) P.hoffs[i + 1] = P.hoffs[i] + c.len[i];
+    P.pay = P.hoffs[m];
+    P.eg.resize(G);
     for (size_t g = 0; g < G; ++g) {
         const Group& gr = c.groups[g];
-        gcell[g] = in_words;
-        in_words += (uint64_t)(gr.p1 - gr.p0) * wpr_of(c.kind, gr.K->E, ktw(*gr.K));
-        eg[g] = EtfGroup{gr.K->etf, gr.p0, gr.p1, nullptr, gr.K->E};
+        P.eg[g] = EtfGroup{gr.K->etf, gr.p0, gr.p1, nullptr, gr.K->E};
+        P.any_wide |= P.orset && gr.K->wide;
     }
     // several namespaces' OR-Set payloads: one decode launch over all of them (a table of
     // the dictionaries rides in the in region) with one plan, else group by group, each
     // with its own plan and segment table
-    bool any_wide = false;
-    for (const Group& g : c.groups) any_wide |= orset && g.K->wide;
-    const bool multi = G > 1 && dec && orset && !any_wide &&
-                       etf_multi_fill(ctx, eg.data(), (uint32_t)G, m, nullptr);
-    std::vector<EtfReadPlan> plans(multi ? 1 : G);
-    for (size_t g = 0; g < plans.size(); ++g) {
+    P.multi = G > 1 && P.dec && P.orset && !P.any_wide &&
+              etf_multi_fill(ctx, P.eg.data(), (uint32_t)G, m, nullptr);
+    P.plans.resize(P.multi ? 1 : G);
+    for (size_t g = 0; g < P.plans.size(); ++g) {
         const Group& gr = c.groups[g];
-        const uint32_t p0 = multi ? 0 : gr.p0, R = multi ? m : gr.p1 - gr.p0;
-        if (dec && orset && R && !gr.K->wide)
-            etf_read_plan(ctx, gr.K->etf, R, hoffs.data() + p0, &plans[g]);
-        gseg[g] = seg_area;
-        if (plans[g].nseg) seg_area += al(4ull * (R + 1), 16);
+        const uint32_t p0 = P.multi ? 0 : gr.p0, R = P.multi ? m : gr.p1 - gr.p0;
+        if (P.dec && P.orset && R && !gr.K->wide)
+            etf_read_plan(ctx, gr.K->etf, R, P.hoffs.data() + p0, &P.plans[g]);
     }
-    const EtfReadPlan& plan = plans[0];
-    const uint64_t mtab_bytes = multi ? al(etf_multi_bytes((uint32_t)G, m), 256) : 0;
-    const bool has_payload_out = c.op == Op::MERGE || c.op == Op::VALUE || c.op == Op::READ ||
-                                 c.op == Op::VVALUE;
-    const uint64_t W = wpr_of(c.kind, E, TW);        // words per replica (single-group ops)
-    // in region (host -> device)
-    // [offsets | segment tables | zeroed words: the size pass's ticket, the decoders' redo
-    //  lists, the one-launch merge's look-back words, the variable kernel's difference words
-    //  and ticket | variable cell pointers, operand cell pointers, widths | the decode
-    //  table of several dictionaries | payloads]
-    const uint64_t i_offs = 0, i_seg = al(8ull * (m + 1), 256),
-                   i_zero = i_seg + al(seg_area, 256),
-                   z_lb = al(4ull * (m + G + 2), 16), z_var = z_lb + 8ull * ((E + 255) / 256),
-                   z_nt = z_var + 4ull * (n + 1), z_bytes = z_nt + 4,
-                   i_vptr = i_zero + al(z_bytes, 256),
-                   i_mtab = i_vptr + (var_op ? al(24ull * n, 256) : 0),
-                   i_pay = i_mtab + mtab_bytes;
-    const uint64_t cells_in = in_words * 8ull;
-    const uint64_t in_bytes = i_pay + (dec ? al(pay + 64, 256) : al(cells_in, 256));
-    // out region: written by kernels into the pinned staging
-    const uint64_t o_st = 0, o_res = al(4ull * m, 16), o_ooff = o_res + al(n, 16),
-                   o_seg = o_ooff + al(8ull * (n + 1), 16);
-    uint64_t o_pay = o_seg;          // (after the segment results of a deferred decode)
+    P.has_payload_out = c.op == Op::MERGE || c.op == Op::VALUE || c.op == Op::READ ||
+                        c.op == Op::VVALUE;
+    // MERGE: the segment decoder's chain check rides on the join's launch (ChainJob), its
+    // per-segment results in a device area of their own after the in region
+    // (one plan only: the join / bind launch carries one chain check)
+    P.defer = (G == 1 || P.multi) && P.dec && P.orset && P.plans[0].nseg && !c.no_defer &&
+              !c.write_only &&
+              ((c.op == Op::MERGE && etf_merge_fused(ctx, n, E)) || P.var_op ||
+               (c.op == Op::VALUE && etf_value_direct(ctx, n, E)));
+    // one operand over binary tokens (a bind, write/4, a threshold, value/1 — no answer
+    // carries token images): tokens the namespace has not seen are taken by the decoder
+    // (NewTok entries into the answer area, registered by run())
+    P.nt_merge = c.op == Op::MERGE && n == 1 && m == 2 && etf_merge_write_one(ctx, K.etf, n, E);
+    P.nt_on = (((P.var_op || c.op == Op::THRESHOLD || c.op == Op::VALUE) && m == 1) ||
+               P.nt_merge) &&
+              G == 1 && P.orset && !K.wide && P.dec && !c.redo.n && !c.write_only &&
+              !c.no_newtok && etf_dict_bin_tokens(K.etf);
+    // a group commit's waiters staged their payloads into pinned blocks of their own while
+    // they waited: gathered to their offsets by the device (k_nif_gather), launched before
+    // the host builds the rest of the pass
+    P.gathered = P.dec && !c.redo.n && !c.write_only &&
+                 std::any_of(c.pre.begin(), c.pre.end(),
+                             [](const uint8_t* x) { return x != nullptr; });
+    return P;
+}
+
+// Where everything of a pass lies: byte offsets into the four blocks of NifState.
+//
+//   in region — staged in S->hin (pinned), pulled to the head of S->dblk:
+//     i_offs   m + 1 payload offsets (u64)
+//     i_seg    the decoders' segment tables, plan g's at gseg[g]
+//     i_zero   z_bytes of words the kernels expect zero (and leave zero or do not reuse):
+//                z_ticket  the size pass's / one-launch merge's ticket
+//                z_redo    segment mode's redo lists: group g's R + 1 words at word p0 + g
+//                z_lb      the one-launch merge's look-back words, one u64 per 256 elements
+//                z_var     the variable kernel's n difference words, then its ticket
+//                z_nt      the decoders' new-token counter
+//     i_vptr   (BIND / WRITE) n pointers to the variables' cells, n to their decoded
+//              operands' cells, n widths in words
+//     i_mtab   (multi) the decode table of several dictionaries
+//     i_pay    the payloads end to end (+ 64 bytes the decoders may read past), or the
+//              host-encoded operand cells
+//   the device block's tail, after the in region (device only):
+//     d_seg    a deferred decode's segment results (kSegResBytes each)
+//     d_vst    (BIND / WRITE) the decode statuses their kernel reads
+//   out region — S->hout (pinned), written by the kernels in place:
+//     o_st     m decode statuses          o_res   n answer bytes
+//     o_ooff   n + 1 answer offsets       o_seg   a failed payload's segment results
+//     o_nt     kNewTokCap NewTok entries  o_pay   ocap bytes of answer payloads
+//   cells — S->dcells: group g's operand cells at word gcell[g] (its payloads' replicas at
+//   its own width), then at byte c_out the answer's cells (MERGE) or value words
+struct PassLayout {
+    uint64_t i_offs = 0, i_seg = 0, i_zero = 0, i_vptr = 0, i_mtab = 0, i_pay = 0, in_bytes = 0;
+    std::vector<uint64_t> gseg;
+    uint64_t z_ticket = 0, z_redo = 4, z_lb = 0, z_var = 0, z_nt = 0, z_bytes = 0;
+    uint64_t d_seg = 0, seg_bytes = 0, d_vst = 0, dblk_bytes = 0;
+    uint64_t o_st = 0, o_res = 0, o_ooff = 0, o_seg = 0, o_nt = 0, o_pay = 0, ocap = 0,
+             out_bytes = 0;
+    std::vector<uint64_t> gcell;
+    uint64_t W = 0;                 // words per replica (single-group ops)
+    uint64_t in_words = 0, cells_in = 0, c_out = 0, dcells_bytes = 0;
+};
+
+// (grows S->ocap to the call's bound: the one thing it decides beyond offsets)
+PassLayout layout_pass(NifState* S, const Call& c, const PassPlan& P) {
+    PassLayout L;
+    const uint32_t m = c.m, n = c.n;
+    const size_t G = c.groups.size();
+    const KindState& K = *c.groups[0].K;
+    const uint32_t E = K.E;
+    uint64_t seg_area = 0;
+    L.gseg.assign(G, 0);
+    L.gcell.assign(G, 0);
+    for (size_t g = 0; g < G; ++g) {
+        const Group& gr = c.groups[g];
+        L.gcell[g] = L.in_words;
+        L.in_words += (uint64_t)(gr.p1 - gr.p0) * wpr_of(c.kind, gr.K->E, ktw(*gr.K));
+    }
+    for (size_t g = 0; g < P.plans.size(); ++g) {
+        const uint32_t R = P.multi ? m : c.groups[g].p1 - c.groups[g].p0;
+        L.gseg[g] = seg_area;
+        if (P.plans[g].nseg) seg_area += al(4ull * (R + 1), 16);
+    }
+    L.W = wpr_of(c.kind, E, ktw(K));
+    L.cells_in = L.in_words * 8ull;
+    L.i_seg = al(8ull * (m + 1), 256);
+    L.i_zero = L.i_seg + al(seg_area, 256);
+    L.z_lb = al(4ull * (m + G + 2), 16);
+    L.z_var = L.z_lb + 8ull * ((E + 255) / 256);
+    L.z_nt = L.z_var + 4ull * (n + 1);
+    L.z_bytes = L.z_nt + 4;
+    L.i_vptr = L.i_zero + al(L.z_bytes, 256);
+    L.i_mtab = L.i_vptr + (P.var_op ? al(24ull * n, 256) : 0);
+    L.i_pay = L.i_mtab + (P.multi ? al(etf_multi_bytes((uint32_t)G, m), 256) : 0);
+    L.in_bytes = L.i_pay + (P.dec ? al(P.pay + 64, 256) : al(L.cells_in, 256));
+    L.d_seg = al(L.in_bytes, 256);
+    L.seg_bytes = P.defer ? al(P.plans[0].nseg * kSegResBytes, 256) : 0;
+    L.d_vst = L.d_seg + L.seg_bytes;
+    L.dblk_bytes = L.d_vst + (P.var_op ? al(4ull * m, 256) : 0);
     // answer payload bound: a merge's image is at most both operands' (flags may be
     // re-encoded one byte longer than a SMALL_ATOM_UTF8 input: the slack, and a second
     // pass when even that is short); value/1's at most its operand's; a variable's image
     // is bounded by nothing the call knows (a second pass when the area is short)
     uint64_t bound = 64ull * n + 64;
     for (uint32_t i = 0; i < m; ++i) bound += c.len[i];
-    if (has_payload_out && S->ocap < bound + bound / 8) S->ocap = al(bound + bound / 8, 1 << 16);
-    const uint64_t ocap = has_payload_out ? S->ocap : 0;
-    // MERGE: the segment decoder's chain check rides on the join's launch (ChainJob), its
-    // per-segment results in a device area of their own after the in region
-    // (one plan only: the join / bind launch carries one chain check)
-    const bool defer = (G == 1 || multi) && dec && orset && plan.nseg && !c.no_defer &&
-                       !c.write_only &&
-                       ((c.op == Op::MERGE && etf_merge_fused(ctx, n, E)) || var_op ||
-                        (c.op == Op::VALUE && etf_value_direct(ctx, n, E)));
-    const uint64_t seg_bytes = defer ? al(plan.nseg * kSegResBytes, 256) : 0;
-    o_pay += seg_bytes;              // (a failed payload's results, written by its chain check)
-    // one operand over binary tokens (a bind, write/4, a threshold, value/1 — no answer
-    // carries token images): tokens the namespace has not seen are taken by the decoder
-    // (NewTok entries into the answer area, registered by run())
-    const bool nt_merge = c.op == Op::MERGE && n == 1 && m == 2 &&
-                          etf_merge_write_one(ctx, K.etf, n, E);
-    const bool nt_on = (((var_op || c.op == Op::THRESHOLD || c.op == Op::VALUE) && m == 1) ||
-                        nt_merge) &&
-                       G == 1 && orset && !K.wide && dec && !c.redo.n && !c.write_only &&
-                       !c.no_newtok && etf_dict_bin_tokens(K.etf);
-    const uint64_t o_nt = o_pay, nt_bytes = nt_on ? al(sizeof(NewTok) * kNewTokCap, 256) : 0;
-    o_pay += nt_bytes;
-    const uint64_t out_bytes = o_pay + ocap;
-    // device statuses of the variable calls (their kernel reads them)
-    const uint64_t vst_bytes = var_op ? al(4ull * m, 256) : 0;
+    if (P.has_payload_out && S->ocap < bound + bound / 8)
+        S->ocap = al(bound + bound / 8, 1 << 16);
+    L.ocap = P.has_payload_out ? S->ocap : 0;
+    L.o_res = al(4ull * m, 16);
+    L.o_ooff = L.o_res + al(n, 16);
+    L.o_seg = L.o_ooff + al(8ull * (n + 1), 16);
+    // (a failed payload's results, written by its chain check)
+    L.o_nt = L.o_seg + L.seg_bytes;
+    L.o_pay = L.o_nt + (P.nt_on ? al(sizeof(NewTok) * kNewTokCap, 256) : 0);
+    L.out_bytes = L.o_pay + L.ocap;
     // cells: in batch m x W words; MERGE: answers n x W; VALUE / VVALUE: value words
     const uint64_t VW = (E + 63ull) / 64ull;
-    const uint64_t cells_out = c.op == Op::MERGE ? (uint64_t)n * W * 8ull
+    const uint64_t cells_out = c.op == Op::MERGE ? (uint64_t)n * L.W * 8ull
                                : (c.op == Op::VALUE || c.op == Op::VVALUE) ? (uint64_t)n * VW * 8ull
                                                                             : 0;
-    const uint64_t c_out = al(cells_in, 256);
-    {
-        Guard g(ctx);
-        if (int s = grow_dev(ctx, &S->dblk, &S->dblk_bytes,
-                             al(in_bytes, 256) + seg_bytes + vst_bytes))
-            return s;
-        const uint64_t had = S->dcells_bytes;
-        if (int s = grow_dev(ctx, &S->dcells, &S->dcells_bytes, c_out + cells_out + 256)) return s;
-        if (S->dcells_bytes != had) S->clean_words = 0;
-        if (int s = grow_host(ctx, &S->hin, &S->hin_bytes, in_bytes)) return s;
-        if (int s = grow_host(ctx, &S->hout, &S->hout_bytes, out_bytes)) return s;
-        // the staging's device addresses (looked up once per allocation: the runtime's
-        // lookup costs host microseconds)
-        void* hd = nullptr;
-        if (S->hin_dkey != S->hin) {
-            LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hin, 0));
-            S->hin_d = static_cast<uint8_t*>(hd);
-            S->hin_dkey = S->hin;
-        }
-        if (S->hout_dkey != S->hout) {
-            LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hout, 0));
-            S->hout_d = static_cast<uint8_t*>(hd);
-            S->hout_dkey = S->hout;
-        }
-        if (var_in)
-            for (laspj_var* v : c.vars)
-                if (int s = fit_var(ctx, v, v->ns->E, v->ns->wide ? v->ns->tw : 1)) return s;
+    L.c_out = al(L.cells_in, 256);
+    L.dcells_bytes = L.c_out + cells_out + 256;
+    return L;
+}
+
+// The pinned staging grown to the two regions, and its device addresses (looked up once per
+// allocation: the runtime's lookup costs host microseconds).  Call with ctx->mu held.
+int fit_staging(laspj_ctx* ctx, NifState* S, uint64_t in_bytes, uint64_t out_bytes) {
+    if (int s = grow_host(ctx, &S->hin, &S->hin_bytes, in_bytes)) return s;
+    if (int s = grow_host(ctx, &S->hout, &S->hout_bytes, out_bytes)) return s;
+    void* hd = nullptr;
+    if (S->hin_dkey != S->hin) {
+        LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hin, 0));
+        S->hin_d = static_cast<uint8_t*>(hd);
+        S->hin_dkey = S->hin;
     }
-    uint8_t* hin = static_cast<uint8_t*>(S->hin);
-    uint8_t* din = static_cast<uint8_t*>(S->dblk);
-    // a group commit's waiters staged their payloads into pinned blocks of their own while
-    // they waited: gathered to their offsets by the device (k_nif_gather), launched before
-    // the host builds the rest of the pass
-    const bool gathered = dec && !c.redo.n && !c.write_only &&
-                          std::any_of(c.pre.begin(), c.pre.end(),
-                                      [](const uint8_t* x) { return x != nullptr; });
+    if (S->hout_dkey != S->hout) {
+        LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hout, 0));
+        S->hout_d = static_cast<uint8_t*>(hd);
+        S->hout_dkey = S->hout;
+    }
+    return LASPJ_OK;
+}
+
+// the four blocks' addresses once they are fitted to a layout
+struct PassMem {
+    uint8_t* hin = nullptr;             // in region: pinned host address,
+    const uint8_t* hin_d = nullptr;     //   the same bytes as the device sees them,
+    uint8_t* din = nullptr;             //   and their device copy (S->dblk)
+    const uint8_t* hout = nullptr;      // out region: as the host reads it,
+    uint8_t* rout = nullptr;            //   as the kernels write it
+    uint64_t *cin = nullptr, *cout = nullptr;   // operand cells, answer cells
+    std::vector<EtfGroup> eg;           // the plan's groups, their cells' addresses filled in
+};
+
+int fit_pass(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+             PassMem* M) {
+    Guard g(ctx);
+    if (int s = grow_dev(ctx, &S->dblk, &S->dblk_bytes, L.dblk_bytes)) return s;
+    const uint64_t had = S->dcells_bytes;
+    if (int s = grow_dev(ctx, &S->dcells, &S->dcells_bytes, L.dcells_bytes)) return s;
+    if (S->dcells_bytes != had) S->clean_words = 0;
+    if (int s = fit_staging(ctx, S, L.in_bytes, L.out_bytes)) return s;
+    if (P.var_in)
+        for (laspj_var* v : c.vars)
+            if (int s = fit_var(ctx, v, v->ns->E, v->ns->wide ? v->ns->tw : 1)) return s;
+    M->hin = static_cast<uint8_t*>(S->hin);
+    M->hin_d = S->hin_d;
+    M->din = static_cast<uint8_t*>(S->dblk);
+    M->hout = static_cast<const uint8_t*>(S->hout);
+    M->rout = S->hout_d;
+    M->cin = static_cast<uint64_t*>(S->dcells);
+    M->cout = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(S->dcells) + L.c_out);
+    M->eg = P.eg;
+    for (size_t k = 0; k < M->eg.size(); ++k) M->eg[k].cells = M->cin + L.gcell[k];
+    return LASPJ_OK;
+}
+
+// payloads for k_nif_gather, launched kGatherMax at a time (call with ctx->mu held)
+struct Gatherer {
+    laspj_ctx* ctx;
+    uint8_t* dst;                   // the payload area on the device
     GatherArgs ga{};
     uint32_t ng = 0;
     uint64_t most = 0;
-    auto gather = [&]() -> int {
+    int flush() {
         if (!ng) return LASPJ_OK;
         // (one wave step of 2 KiB per wave, 8 KiB per block)
         const uint64_t blocks = std::min<uint64_t>((most + 8191) / 8192, (uint64_t)ctx->cus);
         hipLaunchKernelGGL(k_nif_gather, dim3((unsigned)std::max<uint64_t>(blocks, 1), ng),
-                           dim3(256), 0, ctx->stream, ga, din + i_pay);
+                           dim3(256), 0, ctx->stream, ga, dst);
         LJ_LAUNCHED(ctx);
         ng = 0;
         most = 0;
         return LASPJ_OK;
-    };
-    if (gathered) {
+    }
+    int add(const uint8_t* src, uint64_t at, uint64_t len) {
+        ga.d[ng++] = GatherDesc{src, at, len};
+        most = std::max(most, len);
+        return ng == kGatherMax ? flush() : LASPJ_OK;
+    }
+};
+
+// The host's half of staging, outside ctx->mu (group-commit waiters keep queueing behind a
+// pass that builds its head): the payloads the waiters staged themselves set off first,
+// then the head written into the pinned in region and, when the device cannot decode the
+// operands, their cells encoded by the host dictionaries (*hst: their statuses).
+int stage_operands(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                   const PassMem& M, std::vector<int32_t>* hst) {
+    const uint32_t m = c.m, n = c.n;
+    const size_t G = c.groups.size();
+    if (P.gathered) {
         Guard g(ctx);
-        for (uint32_t i = 0; i < m; ++i) {
-            if (!c.len[i] || !c.pre[i]) continue;
-            ga.d[ng++] = GatherDesc{c.pre[i], hoffs[i], c.len[i]};
-            most = std::max(most, c.len[i]);
-            if (ng == kGatherMax)
-                if (int s = gather()) return s;
-        }
-        if (int s = gather()) return s;
+        Gatherer ga{ctx, M.din + L.i_pay};
+        for (uint32_t i = 0; i < m; ++i)
+            if (c.len[i] && c.pre[i])
+                if (int s = ga.add(c.pre[i], P.hoffs[i], c.len[i])) return s;
+        if (int s = ga.flush()) return s;
     }
-    uint8_t* dseg = din + al(in_bytes, 256);          // deferred segment results
-    int32_t* dvst = reinterpret_cast<int32_t*>(dseg + seg_bytes);   // variable calls' statuses
-    uint8_t* rout = S->hout_d;                        // where kernels write the out region
-    const uint8_t* hin_d = S->hin_d;
-    uint64_t* cin = static_cast<uint64_t*>(S->dcells);
-    uint64_t* cout = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(S->dcells) + c_out);
-    std::memcpy(hin + i_offs, hoffs.data(), 8ull * (m + 1));
-    for (size_t g = 0; g < plans.size(); ++g)
-        if (plans[g].nseg)
-            std::memcpy(hin + i_seg + gseg[g], plans[g].segbase.data(),
-                        4ull * plans[g].segbase.size());
-    if (multi) {
-        for (size_t g = 0; g < G; ++g) eg[g].cells = static_cast<uint64_t*>(S->dcells) + gcell[g];
-        etf_multi_fill(ctx, eg.data(), (uint32_t)G, m, hin + i_mtab);
-    }
-    std::memset(hin + i_zero, 0, z_bytes);
-    uint64_t maxw = 0;                                // widest variable (the bind's chunks)
-    if (var_op) {
+    std::memcpy(M.hin + L.i_offs, P.hoffs.data(), 8ull * (m + 1));
+    for (size_t g = 0; g < P.plans.size(); ++g)
+        if (P.plans[g].nseg)
+            std::memcpy(M.hin + L.i_seg + L.gseg[g], P.plans[g].segbase.data(),
+                        4ull * P.plans[g].segbase.size());
+    if (P.multi) etf_multi_fill(ctx, M.eg.data(), (uint32_t)G, m, M.hin + L.i_mtab);
+    std::memset(M.hin + L.i_zero, 0, L.z_bytes);
+    if (P.var_op) {
         // per variable: its cells, its decoded operand's cells, their width
         for (size_t g = 0; g < G; ++g) {
             const Group& gr = c.groups[g];
             const uint64_t w = wpr_of(c.kind, gr.K->E, ktw(*gr.K));
-            maxw = std::max(maxw, w);
             for (uint32_t i = gr.p0; i < gr.p1; ++i) {
                 const uint64_t cur = reinterpret_cast<uint64_t>(c.vars[i]->cells);
                 const uint64_t in = reinterpret_cast<uint64_t>(
-                    static_cast<uint64_t*>(S->dcells) + gcell[g] + (uint64_t)(i - gr.p0) * w);
-                std::memcpy(hin + i_vptr + 8ull * i, &cur, 8);
-                std::memcpy(hin + i_vptr + 8ull * (n + i), &in, 8);
-                std::memcpy(hin + i_vptr + 8ull * (2ull * n + i), &w, 8);
+                    M.cin + L.gcell[g] + (uint64_t)(i - gr.p0) * w);
+                std::memcpy(M.hin + L.i_vptr + 8ull * i, &cur, 8);
+                std::memcpy(M.hin + L.i_vptr + 8ull * (n + i), &in, 8);
+                std::memcpy(M.hin + L.i_vptr + 8ull * (2ull * n + i), &w, 8);
             }
         }
     }
-    uint32_t* dticket = reinterpret_cast<uint32_t*>(din + i_zero);
-    auto* dlb = reinterpret_cast<unsigned long long*>(din + i_zero + z_lb);
-    uint32_t* dvdiff = reinterpret_cast<uint32_t*>(din + i_zero + z_var);
-    const bool clean = S->clean_words >= in_words;
-    std::vector<int32_t> hst;
-    if (m && !dec) {
+    if (m && !P.dec) {
         // token images of several lengths (or no tokens yet): the host dictionaries encode
         // the cells (laspj_dict_encode), the device does the rest
-        std::vector<uint8_t> blob(pay);
+        std::vector<uint8_t> blob(P.pay);
         for (uint32_t i = 0; i < m; ++i)
-            if (c.len[i]) std::memcpy(blob.data() + hoffs[i], c.p[i], c.len[i]);
-        hst.assign(m, 0);
+            if (c.len[i]) std::memcpy(blob.data() + P.hoffs[i], c.p[i], c.len[i]);
+        hst->assign(m, 0);
         for (size_t g = 0; g < G; ++g) {
             const Group& gr = c.groups[g];
             if (gr.p1 == gr.p0) continue;
             if (int s = dict_encode_cells(gr.K->dict, c.kind, blob.data(),
-                                          reinterpret_cast<const uint64_t*>(hoffs.data()) + gr.p0,
+                                          reinterpret_cast<const uint64_t*>(P.hoffs.data()) + gr.p0,
                                           gr.p1 - gr.p0, -1, gr.K->E, ktw(*gr.K),
-                                          reinterpret_cast<uint64_t*>(hin + i_pay) + gcell[g],
-                                          hst.data() + gr.p0))
+                                          reinterpret_cast<uint64_t*>(M.hin + L.i_pay) + L.gcell[g],
+                                          hst->data() + gr.p0))
                 return fail(ctx, s, "nif: host encode failed (%d)", s);
         }
-        ++S->stats[5];
-    }
-    {
-        Guard g(ctx);
-        // the head, then the payloads (or host-encoded cells) a piece at a time: each
-        // piece's pull runs while the host stages the next
-        uint64_t sent = 0;                   // region bytes already pulled
-        auto send = [&](uint64_t upto) -> int {
-            // 16-byte lanes: sent is a multiple of 16 (the head is 256-aligned, pieces
-            // 4096-multiples), upto is rounded up inside the staged region
-            const uint64_t n16 = (al(upto, 16) - sent) / 16;
-            if (!n16) return LASPJ_OK;
-            const uint64_t blocks = std::min<uint64_t>((n16 + 255) / 256, (uint64_t)ctx->cus * 4);
-            hipLaunchKernelGGL(k_nif_pull, dim3((unsigned)std::max<uint64_t>(blocks, 1)),
-                               dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const pull16*>(hin_d + sent),
-                               reinterpret_cast<pull16*>(din + sent), n16);
-            LJ_LAUNCHED(ctx);
-            sent = al(upto, 16);
-            return LASPJ_OK;
-        };
-        if (dec && (c.redo.n || c.write_only)) {
-            // (a redo or write-only pass: the head and payloads the last pass pulled are
-            // still there)
-        } else if (gathered) {
-            // the head, then the payloads not staged by their callers (the leader's own)
-            // copied into the staging and gathered to their offsets (the staged ones are
-            // on their way since the region was allocated)
-            if (int s = send(i_pay)) return s;
-            for (uint32_t i = 0; i < m; ++i) {
-                if (!c.len[i] || c.pre[i]) continue;
-                const uint64_t tc = now_ns();
-                std::memcpy(hin + i_pay + hoffs[i], c.p[i], c.len[i]);
-                t_copy += now_ns() - tc;
-                ga.d[ng++] = GatherDesc{hin_d + i_pay + hoffs[i], hoffs[i], c.len[i]};
-                most = std::max(most, c.len[i]);
-                if (ng == kGatherMax)
-                    if (int s = gather()) return s;
-            }
-            if (int s = gather()) return s;
-        } else if (dec) {
-            uint64_t at = 0;
-            uint32_t i = 0;
-            uint64_t io = 0;                     // offset inside payload i
-            while (i < m && c.len[i] == 0) ++i;
-            while (at < pay) {
-                const uint64_t piece = std::min(kPullPiece, pay - at);
-                uint64_t done = 0;
-                const uint64_t tc = now_ns();
-                while (done < piece) {
-                    const uint64_t take = std::min(piece - done, c.len[i] - io);
-                    std::memcpy(hin + i_pay + at + done, c.p[i] + io, take);
-                    done += take;
-                    io += take;
-                    if (io == c.len[i]) {
-                        ++i;
-                        io = 0;
-                        while (i < m && c.len[i] == 0) ++i;
-                    }
-                }
-                t_copy += now_ns() - tc;
-                at += piece;
-                if (int s = send(i_pay + at)) return s;
-            }
-            if (pay == 0)
-                if (int s = send(i_pay)) return s;
-        } else {
-            // the head and (when there are operands) the host-encoded cells
-            if (int s = send(i_pay)) return s;
-            if (m) LJ_HIP(ctx, hipMemcpyAsync(cin, hin + i_pay, cells_in, hipMemcpyHostToDevice,
-                                              ctx->stream));
-        }
-        laspj_batch inb = view(ctx, c.kind, m, E, cin, TW);
-        // statuses: straight into the pinned answer, or (variable calls) device memory their
-        // kernel reads and publishes
-        int32_t* dst = var_op ? dvst : reinterpret_cast<int32_t*>(rout + o_st);
-        ChainJob cjob;
-        if (defer) {
-            cjob.res = dseg;
-            cjob.hres = rout + o_seg;
-        }
-        if (c.write_only) {
-            // (the operands' cells the last pass decoded are still there)
-        } else if (dec && multi) {
-            // every namespace's payloads in one launch (the cells zeroed first when the last
-            // call left them dirty: the decoders only set what they decode)
-            if (!clean && !c.redo.n) LJ_HIP(ctx, hipMemsetAsync(cin, 0, cells_in, ctx->stream));
-            if (int s = etf_read_multi_enqueue(
-                    ctx, eg.data(), (uint32_t)G, din + i_mtab, m, din + i_pay, pay,
-                    reinterpret_cast<const unsigned long long*>(din + i_offs), plan,
-                    plan.nseg ? reinterpret_cast<const uint32_t*>(din + i_seg) : nullptr, dst,
-                    defer ? &cjob : nullptr, c.redo.n ? &c.redo : nullptr))
-                return s;
-        } else if (dec) {
-            // each group's payloads against its own dictionary (offsets are absolute in the
-            // payload area, so a group reads its slice of them in place)
-            for (size_t g = 0; g < G; ++g) {
-                const Group& gr = c.groups[g];
-                const uint32_t R = gr.p1 - gr.p0;
-                if (!R) continue;
-                laspj_batch gb = view(ctx, c.kind, R, gr.K->E, cin + gcell[g]);
-                const auto* doffs = reinterpret_cast<const unsigned long long*>(din + i_offs) + gr.p0;
-                NewTokArgs nta;
-                if (nt_on) {
-                    if (!++S->nt_seq) ++S->nt_seq;           // (0 never tags an entry)
-                    nta = NewTokArgs{reinterpret_cast<uint32_t*>(din + i_zero + z_nt),
-                                     reinterpret_cast<NewTok*>(rout + o_nt), kNewTokCap,
-                                     S->nt_seq};
-                }
-                if (orset) {
-                    if (int s = etf_read_enqueue(
-                            ctx, &gb, gr.K->etf, -1, 1, din + i_pay, pay, doffs, plans[g],
-                            plans[g].nseg ? reinterpret_cast<const uint32_t*>(din + i_seg + gseg[g])
-                                          : nullptr,
-                            dst + gr.p0, !clean && !c.redo.n, dticket + 1 + gr.p0 + g,
-                            defer ? &cjob : nullptr, c.redo.n ? &c.redo : nullptr,
-                            nt_on ? &nta : nullptr))
-                        return s;
-                } else if (int s = gset_read_enqueue(ctx, &gb, gr.K->etf, -1, 1, din + i_pay, doffs,
-                                                     dst + gr.p0, !clean, hoffs.data() + gr.p0)) {
-                    return s;
-                }
-            }
-        } else if (m && var_op) {
-            LJ_HIP(ctx, hipMemcpyAsync(dvst, hst.data(), 4ull * m, hipMemcpyHostToDevice,
-                                       ctx->stream));
-        }
-        laspj_batch lhs = view(ctx, c.kind, n, E, cin, TW);
-        laspj_batch rhs = view(ctx, c.kind, n, E, cin + (uint64_t)n * W, TW);
-        auto* dooff = reinterpret_cast<unsigned long long*>(rout + o_ooff);
-        uint8_t* dopay = rout + o_pay;
-        switch (c.op) {
-        case Op::MERGE: {
-            // lasp_orset:merge/2 (lasp_orset.erl:128-134): the nested orddict:merge of two
-            // canonical orddicts is the slot-wise OR of their cells; lasp_gset:merge/2
-            // (lasp_gset.erl:99-101): ordsets:union of two ordsets, the OR of their bits
-            laspj_batch ob = view(ctx, c.kind, n, E, cout, TW);
-            const unsigned long long* chunks = nullptr;
-            if (wide) {
-                // elements past 64 tokens: the OR, then the wide size pass and writer
-                LJ_HIP(ctx, launch_or(ctx, cout, lhs.dev, rhs.dev, (uint64_t)n * W));
-                if (int s = wide_size_enqueue(ctx, K.wd, cout, n, -1, dooff, ctx->flag)) return s;
-                if (int s = wide_write_enqueue(ctx, K.wd, cout, n, -1, 1, dooff, dopay, ocap))
-                    return s;
-                S->clean_words = 0;
-                break;
-            }
-            if (orset && etf_merge_write_one(ctx, K.etf, n, E)) {
-                // one answer: join, size pass and writer in one launch (look-back), the
-                // operands cleared behind it, the chain checks riding along
-                if (int s = etf_merge_write_enqueue(
-                        ctx, lhs.dev, rhs.dev, E, K.etf, -1, 1, dooff, dopay, ocap, dlb, dticket,
-                        &cjob,
-                        nt_on ? reinterpret_cast<const uint32_t*>(din + i_zero + z_nt) : nullptr))
-                    return s;
-                S->clean_words = in_words;
-                break;
-            }
-            if (!orset && etf_value_direct(ctx, n, E)) {
-                // few long G-Set answers: written from both operands' bits
-                if (int s = etf_gset_merge_write_enqueue(ctx, &lhs, &rhs, K.etf, -1, 1, dooff,
-                                                         ctx->flag, dopay, ocap))
-                    return s;
-                S->clean_words = 0;
-                break;
-            }
-            if (orset && etf_merge_fused(ctx, n, E)) {
-                // the OR fused with the answer's size pass, the operands cleared behind it
-                if (int s = etf_merge_size_enqueue(ctx, lhs.dev, rhs.dev, &ob, K.etf, -1, dooff,
-                                                   ctx->flag, dticket, &chunks, &cjob))
-                    return s;
-                S->clean_words = in_words;
-            } else {
-                LJ_HIP(ctx, launch_or(ctx, cout, lhs.dev, rhs.dev, (uint64_t)n * W));
-                if (int s = etf_size_enqueue(ctx, &ob, K.etf, c.kind, -1, dooff, ctx->flag,
-                                             &chunks))
-                    return s;
-                S->clean_words = 0;
-            }
-            if (int s = etf_write_enqueue(ctx, &ob, K.etf, c.kind, -1, 1, dooff, dopay, ocap,
-                                          chunks))
-                return s;
-            break;
-        }
-        case Op::VALUE:
-        case Op::VVALUE: {
-            // value/1 (lasp_orset.erl:67-73): the elements with a {_, false} token, as the
-            // ordset image the G-Set writer gives a bit row (term_to_binary of the keys)
-            // (VVALUE has no operand cells: its value bits land where they would start)
-            laspj_batch src = c.op == Op::VALUE ? inb : view(ctx, c.kind, 1, E, c.vars[0]->cells, TW);
-            if (wide) {
-                // the value bits of the wide cells, then the G-Set writer over the element images
-                S->clean_words = 0;
-                LJ_HIP(ctx, launch_wide_value(ctx, &src, cout, false));
-                laspj_batch vb = view(ctx, LASPJ_KIND_GSET, n, E, cout);
-                const unsigned long long* chunks = nullptr;
-                if (int s = etf_size_enqueue(ctx, &vb, K.etf, LASPJ_KIND_GSET, -1, dooff, ctx->flag,
-                                             &chunks))
-                    return s;
-                if (int s = etf_write_enqueue(ctx, &vb, K.etf, LASPJ_KIND_GSET, -1, 1, dooff, dopay,
-                                              ocap, chunks))
-                    return s;
-                break;
-            }
-            if (c.kind == LASPJ_KIND_ORSET && etf_value_direct(ctx, n, E)) {
-                // few long answers: written from the cells (no value bits in between), a
-                // decoded operand's cells cleared behind the reads
-                if (int s = etf_value_write_enqueue(ctx, &src, K.etf, -1, 1, dooff, ctx->flag,
-                                                    dopay, ocap, c.op == Op::VALUE, &cjob))
-                    return s;
-                S->clean_words = c.op == Op::VALUE ? in_words : S->clean_words;
-                break;
-            }
-            S->clean_words = 0;
-            LJ_HIP(ctx, launch_orset_value(ctx, &src, cout, false));
-            laspj_batch vb = view(ctx, LASPJ_KIND_GSET, n, E, cout);
-            const unsigned long long* chunks = nullptr;
-            if (int s = etf_size_enqueue(ctx, &vb, K.etf, LASPJ_KIND_GSET, -1, dooff, ctx->flag,
-                                         &chunks))
-                return s;
-            if (int s = etf_write_enqueue(ctx, &vb, K.etf, LASPJ_KIND_GSET, -1, 1, dooff, dopay,
-                                          ocap, chunks))
-                return s;
-            break;
-        }
-        case Op::READ: {
-            // the variable's value as its term_to_binary image (#dv.value read back)
-            laspj_batch vb = view(ctx, c.kind, 1, E, c.vars[0]->cells, TW);
-            if (wide) {
-                if (int s = wide_size_enqueue(ctx, K.wd, vb.dev, 1, -1, dooff, ctx->flag)) return s;
-                if (int s = wide_write_enqueue(ctx, K.wd, vb.dev, 1, -1, 1, dooff, dopay, ocap))
-                    return s;
-                break;
-            }
-            const unsigned long long* chunks = nullptr;
-            if (int s = etf_size_enqueue(ctx, &vb, K.etf, c.kind, -1, dooff, ctx->flag, &chunks))
-                return s;
-            if (int s = etf_write_enqueue(ctx, &vb, K.etf, c.kind, -1, 1, dooff, dopay, ocap,
-                                          chunks))
-                return s;
-            break;
-        }
-        case Op::EQUAL:
-            S->clean_words = 0;
-            // equal/2 (lasp_orset.erl:136-138, lasp_gset.erl:103-105): A == B
-            LJ_HIP(ctx, launch_equal(ctx, &lhs, &rhs, rout + o_res));
-            break;
-        case Op::INFLATION:
-            S->clean_words = 0;
-            // is_inflation / is_strict_inflation (lasp_lattice.erl:137-161, 212-253)
-            LJ_HIP(ctx, wide ? launch_wide_inflation(ctx, &lhs, &rhs, c.strict != 0, rout + o_res)
-                        : orset ? launch_orset_inflation(ctx, &lhs, &rhs, c.strict != 0, rout + o_res)
-                              : launch_gset_inflation(ctx, &lhs, &rhs, c.strict != 0, rout + o_res));
-            break;
-        case Op::THRESHOLD: {
-            // threshold_met(Type, Value, Threshold) (lasp_lattice.erl:62-75): is_(strict_)
-            // inflation(Threshold, Value) with Value the resident cells
-            S->clean_words = 0;
-            laspj_batch cur = view(ctx, c.kind, 1, E, c.vars[0]->cells, TW);
-            LJ_HIP(ctx, wide ? launch_wide_inflation(ctx, &lhs, &cur, c.strict != 0, rout + o_res)
-                        : orset ? launch_orset_inflation(ctx, &lhs, &cur, c.strict != 0, rout + o_res)
-                              : launch_gset_inflation(ctx, &lhs, &cur, c.strict != 0, rout + o_res));
-            break;
-        }
-        case Op::BIND:
-        case Op::WRITE: {
-            // bind/3 (lasp_core.erl:291-312) / write/4 (:839-844) into the resident cells
-            // (the segment decoder's chain check rides on this launch when deferred)
-            if (int s = var_bind_enqueue(ctx, reinterpret_cast<uint64_t* const*>(din + i_vptr),
-                                         reinterpret_cast<uint64_t* const*>(din + i_vptr + 8ull * n),
-                                         reinterpret_cast<const uint64_t*>(din + i_vptr + 16ull * n),
-                                         maxw, n, dvst, dvdiff, dvdiff + n, rout + o_res,
-                                         reinterpret_cast<int32_t*>(rout + o_st),
-                                         c.op == Op::WRITE, &cjob))
-                return s;
-            S->clean_words = in_words;
-            break;
-        }
-        }
-        const uint64_t t1 = now_ns();
-        LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const uint64_t t2 = now_ns();
-        ++S->stats[1];
-        S->stats[8] += t1 - t0;
-        S->stats[9] += t2 - t1;
-        S->stats[11] += t_copy;
-        const uint8_t* hout = static_cast<const uint8_t*>(S->hout);
-        c.st.assign(m, 0);
-        if (dec || var_op) std::memcpy(c.st.data(), hout + o_st, 4ull * m);
-        else c.st = hst;
-        c.newtoks.clear();
-        c.nt_met = false;
-        if (nt_on) {
-            // the decoder's new tokens: the entries tagged with this pass, in the order the
-            // device numbered them
-            const NewTok* ents = reinterpret_cast<const NewTok*>(hout + o_nt);
-            uint32_t k = 0;
-            while (k < kNewTokCap && ents[k].seq == S->nt_seq) ++k;
-            c.nt_met = k != 0;
-            bool ok = true;
-            for (uint32_t i = 0; i < m; ++i) ok &= c.st[i] == LASPJ_DEC_OK;
-            if (k && ok) c.newtoks.assign(ents, ents + k);
-            // (a merge's writer then wrote nothing and left the operands' cells)
-            if (k && c.op == Op::MERGE) S->clean_words = 0;
-        }
-        if (var_op)
-            for (int32_t x : c.st)
-                if (x != LASPJ_DEC_OK) S->clean_words = 0;   // (its cells were kept)
-        c.has_seg = false;
-        if (defer && cjob.armed &&
-            std::find(c.st.begin(), c.st.end(), (int32_t)LASPJ_DEC_UNKNOWN_TERM) != c.st.end()) {
-            // (the chain checks copied the failed payloads' results into the answer area;
-            // those of payloads that decoded are not read)
-            c.segres.resize(8ull * plan.nseg);
-            std::memcpy(c.segres.data(), hout + o_seg, kSegResBytes * plan.nseg);
-            c.segbase = plan.segbase;
-            c.segS = plan.S;
-            c.has_seg = true;
-        }
-        c.res.assign(hout + o_res, hout + o_res + n);
-        if (has_payload_out) {
-            c.ooff.resize(n + 1ull);
-            std::memcpy(c.ooff.data(), hout + o_ooff, 8ull * (n + 1));
-            const uint64_t total = c.ooff[n];
-            if (total > ocap) {
-                // the writer wrote nothing: a larger answer area, the encode again
-                S->ocap = al(total + total / 4, 1 << 16);
-                return -1000;            // caller re-runs the pass
-            }
-            c.obase = hout + o_pay;
-        }
-        S->stats[10] += now_ns() - t2;
+        ++S->stats[ST_HOST_ENCODED];
     }
     return LASPJ_OK;
+}
+
+// The device's half (ctx->mu held): the head, then the payloads (or host-encoded cells) a
+// piece at a time — each piece's pull runs while the host stages the next.  *t_copy: the
+// host nanoseconds spent copying operands into pinned memory.
+int pull_operands(laspj_ctx* ctx, Call& c, const PassPlan& P, const PassLayout& L,
+                  const PassMem& M, uint64_t* t_copy) {
+    const uint32_t m = c.m;
+    uint64_t sent = 0;                   // region bytes already pulled
+    auto send = [&](uint64_t upto) -> int {
+        // 16-byte lanes: sent is a multiple of 16 (the head is 256-aligned, pieces
+        // 4096-multiples), upto is rounded up inside the staged region
+        const uint64_t n16 = (al(upto, 16) - sent) / 16;
+        if (!n16) return LASPJ_OK;
+        const uint64_t blocks = std::min<uint64_t>((n16 + 255) / 256, (uint64_t)ctx->cus * 4);
+        hipLaunchKernelGGL(k_nif_pull, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0,
+                           ctx->stream, reinterpret_cast<const pull16*>(M.hin_d + sent),
+                           reinterpret_cast<pull16*>(M.din + sent), n16);
+        LJ_LAUNCHED(ctx);
+        sent = al(upto, 16);
+        return LASPJ_OK;
+    };
+    if (P.dec && (c.redo.n || c.write_only)) {
+        // (a redo or write-only pass: the head and payloads the last pass pulled are
+        // still there)
+    } else if (P.gathered) {
+        // the head, then the payloads not staged by their callers (the leader's own)
+        // copied into the staging and gathered to their offsets (the staged ones are
+        // on their way since the region was allocated)
+        if (int s = send(L.i_pay)) return s;
+        Gatherer ga{ctx, M.din + L.i_pay};
+        for (uint32_t i = 0; i < m; ++i) {
+            if (!c.len[i] || c.pre[i]) continue;
+            const uint64_t tc = now_ns();
+            std::memcpy(M.hin + L.i_pay + P.hoffs[i], c.p[i], c.len[i]);
+            *t_copy += now_ns() - tc;
+            if (int s = ga.add(M.hin_d + L.i_pay + P.hoffs[i], P.hoffs[i], c.len[i])) return s;
+        }
+        if (int s = ga.flush()) return s;
+    } else if (P.dec) {
+        uint64_t at = 0;
+        uint32_t i = 0;
+        uint64_t io = 0;                     // offset inside payload i
+        while (i < m && c.len[i] == 0) ++i;
+        while (at < P.pay) {
+            const uint64_t piece = std::min(kPullPiece, P.pay - at);
+            uint64_t done = 0;
+            const uint64_t tc = now_ns();
+            while (done < piece) {
+                const uint64_t take = std::min(piece - done, c.len[i] - io);
+                std::memcpy(M.hin + L.i_pay + at + done, c.p[i] + io, take);
+                done += take;
+                io += take;
+                if (io == c.len[i]) {
+                    ++i;
+                    io = 0;
+                    while (i < m && c.len[i] == 0) ++i;
+                }
+            }
+            *t_copy += now_ns() - tc;
+            at += piece;
+            if (int s = send(L.i_pay + at)) return s;
+        }
+        if (P.pay == 0)
+            if (int s = send(L.i_pay)) return s;
+    } else {
+        // the head and (when there are operands) the host-encoded cells
+        if (int s = send(L.i_pay)) return s;
+        if (m) LJ_HIP(ctx, hipMemcpyAsync(M.cin, M.hin + L.i_pay, L.cells_in,
+                                          hipMemcpyHostToDevice, ctx->stream));
+    }
+    return LASPJ_OK;
+}
+
+// where the decoders (or the host) leave the m decode statuses: straight in the pinned
+// answer, or (variable calls) device memory their kernel reads and publishes
+int32_t* status_area(const PassPlan& P, const PassLayout& L, const PassMem& M) {
+    return reinterpret_cast<int32_t*>(P.var_op ? M.din + L.d_vst : M.rout + L.o_st);
+}
+
+// The operands' cells: decoded by the device — every namespace's payloads in one launch, or
+// group by group — or, host-encoded, only their statuses uploaded for the variable kernel.
+// *cjob: armed when the chain check is left to the answer's launch.
+int enqueue_decode(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                   const PassMem& M, const std::vector<int32_t>& hst, ChainJob* cjob) {
+    const uint32_t m = c.m;
+    const size_t G = c.groups.size();
+    const bool clean = S->clean_words >= L.in_words;
+    int32_t* dst = status_area(P, L, M);
+    const auto* doffs_all = reinterpret_cast<const unsigned long long*>(M.din + L.i_offs);
+    if (P.defer) {
+        cjob->res = M.din + L.d_seg;
+        cjob->hres = M.rout + L.o_seg;
+    }
+    if (c.write_only) {
+        // (the operands' cells the last pass decoded are still there)
+    } else if (P.dec && P.multi) {
+        // every namespace's payloads in one launch (the cells zeroed first when the last
+        // call left them dirty: the decoders only set what they decode)
+        const EtfReadPlan& plan = P.plans[0];
+        if (!clean && !c.redo.n) LJ_HIP(ctx, hipMemsetAsync(M.cin, 0, L.cells_in, ctx->stream));
+        if (int s = etf_read_multi_enqueue(
+                ctx, M.eg.data(), (uint32_t)G, M.din + L.i_mtab, m, M.din + L.i_pay, P.pay,
+                doffs_all, plan,
+                plan.nseg ? reinterpret_cast<const uint32_t*>(M.din + L.i_seg) : nullptr, dst,
+                P.defer ? cjob : nullptr, c.redo.n ? &c.redo : nullptr))
+            return s;
+    } else if (P.dec) {
+        // each group's payloads against its own dictionary (offsets are absolute in the
+        // payload area, so a group reads its slice of them in place)
+        for (size_t g = 0; g < G; ++g) {
+            const Group& gr = c.groups[g];
+            const uint32_t R = gr.p1 - gr.p0;
+            if (!R) continue;
+            laspj_batch gb = view(ctx, c.kind, R, gr.K->E, M.cin + L.gcell[g]);
+            const auto* doffs = doffs_all + gr.p0;
+            NewTokArgs nta;
+            if (P.nt_on) {
+                if (!++S->nt_seq) ++S->nt_seq;           // (0 never tags an entry)
+                nta = NewTokArgs{reinterpret_cast<uint32_t*>(M.din + L.i_zero + L.z_nt),
+                                 reinterpret_cast<NewTok*>(M.rout + L.o_nt), kNewTokCap,
+                                 S->nt_seq};
+            }
+            if (P.orset) {
+                const EtfReadPlan& plan = P.plans[g];
+                if (int s = etf_read_enqueue(
+                        ctx, &gb, gr.K->etf, -1, 1, M.din + L.i_pay, P.pay, doffs, plan,
+                        plan.nseg ? reinterpret_cast<const uint32_t*>(M.din + L.i_seg + L.gseg[g])
+                                  : nullptr,
+                        dst + gr.p0, !clean && !c.redo.n,
+                        reinterpret_cast<uint32_t*>(M.din + L.i_zero + L.z_redo) + gr.p0 + g,
+                        P.defer ? cjob : nullptr, c.redo.n ? &c.redo : nullptr,
+                        P.nt_on ? &nta : nullptr))
+                    return s;
+            } else if (int s = gset_read_enqueue(ctx, &gb, gr.K->etf, -1, 1, M.din + L.i_pay,
+                                                 doffs, dst + gr.p0, !clean,
+                                                 P.hoffs.data() + gr.p0)) {
+                return s;
+            }
+        }
+    } else if (m && P.var_op) {
+        LJ_HIP(ctx, hipMemcpyAsync(dst, hst.data(), 4ull * m, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return LASPJ_OK;
+}
+
+// what every answer's enqueue works on: the single-group call's dictionary and the views of
+// its operand cells, the answer's offsets and payload area in the pinned out region
+struct AnswerArgs {
+    KindState& K;
+    uint32_t E, TW;
+    laspj_batch lhs, rhs;           // operands [0, n) and [n, 2n)
+    unsigned long long* dooff;
+    uint8_t* dopay;
+    uint8_t* dres;                  // n answer bytes
+};
+
+// an answer's images from its cells: the size pass, then the writer over its offsets
+int size_and_write(laspj_ctx* ctx, const laspj_batch* b, int32_t kind, const AnswerArgs& a,
+                   uint64_t ocap) {
+    const unsigned long long* chunks = nullptr;
+    if (int s = etf_size_enqueue(ctx, b, a.K.etf, kind, -1, a.dooff, ctx->flag, &chunks)) return s;
+    return etf_write_enqueue(ctx, b, a.K.etf, kind, -1, 1, a.dooff, a.dopay, ocap, chunks);
+}
+
+// the same over a wide namespace's cells
+int wide_size_and_write(laspj_ctx* ctx, uint64_t* cells, uint32_t n, const AnswerArgs& a,
+                        uint64_t ocap) {
+    if (int s = wide_size_enqueue(ctx, a.K.wd, cells, n, -1, a.dooff, ctx->flag)) return s;
+    return wide_write_enqueue(ctx, a.K.wd, cells, n, -1, 1, a.dooff, a.dopay, ocap);
+}
+
+// lasp_orset:merge/2 (lasp_orset.erl:128-134): the nested orddict:merge of two canonical
+// orddicts is the slot-wise OR of their cells; lasp_gset:merge/2 (lasp_gset.erl:99-101):
+// ordsets:union of two ordsets, the OR of their bits
+int answer_merge(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                 const PassMem& M, const AnswerArgs& a, const ChainJob* cjob) {
+    const uint32_t n = c.n;
+    laspj_batch ob = view(ctx, c.kind, n, a.E, M.cout, a.TW);
+    uint8_t* dzero = M.din + L.i_zero;
+    uint32_t* dticket = reinterpret_cast<uint32_t*>(dzero + L.z_ticket);
+    if (P.wide) {
+        // elements past 64 tokens: the OR, then the wide size pass and writer
+        LJ_HIP(ctx, launch_or(ctx, M.cout, a.lhs.dev, a.rhs.dev, (uint64_t)n * L.W));
+        if (int s = wide_size_and_write(ctx, M.cout, n, a, L.ocap)) return s;
+        S->clean_words = 0;
+        return LASPJ_OK;
+    }
+    if (P.orset && etf_merge_write_one(ctx, a.K.etf, n, a.E)) {
+        // one answer: join, size pass and writer in one launch (look-back), the
+        // operands cleared behind it, the chain checks riding along
+        if (int s = etf_merge_write_enqueue(
+                ctx, a.lhs.dev, a.rhs.dev, a.E, a.K.etf, -1, 1, a.dooff, a.dopay, L.ocap,
+                reinterpret_cast<unsigned long long*>(dzero + L.z_lb), dticket, cjob,
+                P.nt_on ? reinterpret_cast<const uint32_t*>(dzero + L.z_nt) : nullptr))
+            return s;
+        S->clean_words = L.in_words;
+        return LASPJ_OK;
+    }
+    if (!P.orset && etf_value_direct(ctx, n, a.E)) {
+        // few long G-Set answers: written from both operands' bits
+        if (int s = etf_gset_merge_write_enqueue(ctx, &a.lhs, &a.rhs, a.K.etf, -1, 1, a.dooff,
+                                                 ctx->flag, a.dopay, L.ocap))
+            return s;
+        S->clean_words = 0;
+        return LASPJ_OK;
+    }
+    if (P.orset && etf_merge_fused(ctx, n, a.E)) {
+        // the OR fused with the answer's size pass, the operands cleared behind it
+        const unsigned long long* chunks = nullptr;
+        if (int s = etf_merge_size_enqueue(ctx, a.lhs.dev, a.rhs.dev, &ob, a.K.etf, -1, a.dooff,
+                                           ctx->flag, dticket, &chunks, cjob))
+            return s;
+        S->clean_words = L.in_words;
+        return etf_write_enqueue(ctx, &ob, a.K.etf, c.kind, -1, 1, a.dooff, a.dopay, L.ocap,
+                                 chunks);
+    }
+    LJ_HIP(ctx, launch_or(ctx, M.cout, a.lhs.dev, a.rhs.dev, (uint64_t)n * L.W));
+    S->clean_words = 0;
+    return size_and_write(ctx, &ob, c.kind, a, L.ocap);
+}
+
+// value/1 (lasp_orset.erl:67-73): the elements with a {_, false} token, as the ordset image
+// the G-Set writer gives a bit row (term_to_binary of the keys)
+// (VVALUE has no operand cells: its value bits land where they would start)
+int answer_value(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                 const PassMem& M, const AnswerArgs& a, const ChainJob* cjob) {
+    const uint32_t n = c.n;
+    laspj_batch src = c.op == Op::VALUE ? view(ctx, c.kind, c.m, a.E, M.cin, a.TW)
+                                        : view(ctx, c.kind, 1, a.E, c.vars[0]->cells, a.TW);
+    if (!P.wide && P.orset && etf_value_direct(ctx, n, a.E)) {
+        // few long answers: written from the cells (no value bits in between), a
+        // decoded operand's cells cleared behind the reads
+        if (int s = etf_value_write_enqueue(ctx, &src, a.K.etf, -1, 1, a.dooff, ctx->flag, a.dopay,
+                                            L.ocap, c.op == Op::VALUE, cjob))
+            return s;
+        S->clean_words = c.op == Op::VALUE ? L.in_words : S->clean_words;
+        return LASPJ_OK;
+    }
+    // the value bits of the (wide) cells, then the G-Set writer over the element images
+    S->clean_words = 0;
+    LJ_HIP(ctx, P.wide ? launch_wide_value(ctx, &src, M.cout, false)
+                       : launch_orset_value(ctx, &src, M.cout, false));
+    laspj_batch vb = view(ctx, LASPJ_KIND_GSET, n, a.E, M.cout);
+    return size_and_write(ctx, &vb, LASPJ_KIND_GSET, a, L.ocap);
+}
+
+// the variable's value as its term_to_binary image (#dv.value read back)
+int answer_read(laspj_ctx* ctx, Call& c, const PassPlan& P, const PassLayout& L, const AnswerArgs& a) {
+    laspj_batch vb = view(ctx, c.kind, 1, a.E, c.vars[0]->cells, a.TW);
+    if (P.wide) return wide_size_and_write(ctx, vb.dev, 1, a, L.ocap);
+    return size_and_write(ctx, &vb, c.kind, a, L.ocap);
+}
+
+// is_inflation / is_strict_inflation (lasp_lattice.erl:137-161, 212-253) of prev -> cur
+hipError_t launch_inflation(laspj_ctx* ctx, const PassPlan& P, const laspj_batch* prev,
+                            const laspj_batch* cur, bool strict, uint8_t* out) {
+    return P.wide    ? launch_wide_inflation(ctx, prev, cur, strict, out)
+           : P.orset ? launch_orset_inflation(ctx, prev, cur, strict, out)
+                     : launch_gset_inflation(ctx, prev, cur, strict, out);
+}
+
+int answer_compare(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const AnswerArgs& a) {
+    S->clean_words = 0;
+    if (c.op == Op::EQUAL) {
+        // equal/2 (lasp_orset.erl:136-138, lasp_gset.erl:103-105): A == B
+        LJ_HIP(ctx, launch_equal(ctx, &a.lhs, &a.rhs, a.dres));
+    } else if (c.op == Op::INFLATION) {
+        LJ_HIP(ctx, launch_inflation(ctx, P, &a.lhs, &a.rhs, c.strict != 0, a.dres));
+    } else {
+        // threshold_met(Type, Value, Threshold) (lasp_lattice.erl:62-75): is_(strict_)
+        // inflation(Threshold, Value) with Value the resident cells
+        laspj_batch cur = view(ctx, c.kind, 1, a.E, c.vars[0]->cells, a.TW);
+        LJ_HIP(ctx, launch_inflation(ctx, P, &a.lhs, &cur, c.strict != 0, a.dres));
+    }
+    return LASPJ_OK;
+}
+
+// bind/3 (lasp_core.erl:291-312) / write/4 (:839-844) into the resident cells (the segment
+// decoder's chain check rides on this launch when deferred)
+int answer_bind(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                const PassMem& M, const AnswerArgs& a, const ChainJob* cjob) {
+    const uint32_t n = c.n;
+    uint64_t maxw = 0;                                // widest variable (the bind's chunks)
+    for (const Group& gr : c.groups) maxw = std::max(maxw, wpr_of(c.kind, gr.K->E, ktw(*gr.K)));
+    uint32_t* dvdiff = reinterpret_cast<uint32_t*>(M.din + L.i_zero + L.z_var);
+    if (int s = var_bind_enqueue(ctx, reinterpret_cast<uint64_t* const*>(M.din + L.i_vptr),
+                                 reinterpret_cast<uint64_t* const*>(M.din + L.i_vptr + 8ull * n),
+                                 reinterpret_cast<const uint64_t*>(M.din + L.i_vptr + 16ull * n),
+                                 maxw, n, status_area(P, L, M), dvdiff, dvdiff + n, a.dres,
+                                 reinterpret_cast<int32_t*>(M.rout + L.o_st), c.op == Op::WRITE,
+                                 cjob))
+        return s;
+    S->clean_words = L.in_words;
+    return LASPJ_OK;
+}
+
+// The op's answer over the decoded cells, written by the kernels into the pinned out region.
+int enqueue_answer(laspj_ctx* ctx, NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                   const PassMem& M, const ChainJob* cjob) {
+    KindState& K = *c.groups[0].K;
+    const uint32_t E = K.E, TW = ktw(K);
+    AnswerArgs a{K, E, TW, view(ctx, c.kind, c.n, E, M.cin, TW),
+                 view(ctx, c.kind, c.n, E, M.cin + (uint64_t)c.n * L.W, TW),
+                 reinterpret_cast<unsigned long long*>(M.rout + L.o_ooff), M.rout + L.o_pay,
+                 M.rout + L.o_res};
+    switch (c.op) {
+    case Op::MERGE: return answer_merge(ctx, S, c, P, L, M, a, cjob);
+    case Op::VALUE:
+    case Op::VVALUE: return answer_value(ctx, S, c, P, L, M, a, cjob);
+    case Op::READ: return answer_read(ctx, c, P, L, a);
+    case Op::EQUAL:
+    case Op::INFLATION:
+    case Op::THRESHOLD: return answer_compare(ctx, S, c, P, a);
+    case Op::BIND:
+    case Op::WRITE: return answer_bind(ctx, S, c, P, L, M, a, cjob);
+    }
+    return LASPJ_OK;
+}
+
+// After the synchronise: statuses, new tokens, a deferred pass's segment results and the
+// answers read from the pinned out region into the call.  kPassAgain: the answer area was
+// short (it has been grown).
+int collect_answers(NifState* S, Call& c, const PassPlan& P, const PassLayout& L,
+                    const PassMem& M, const std::vector<int32_t>& hst, const ChainJob& cjob) {
+    const uint32_t m = c.m, n = c.n;
+    const uint8_t* hout = M.hout;
+    c.st.assign(m, 0);
+    if (P.dec || P.var_op) std::memcpy(c.st.data(), hout + L.o_st, 4ull * m);
+    else c.st = hst;
+    c.newtoks.clear();
+    c.nt_met = false;
+    if (P.nt_on) {
+        // the decoder's new tokens: the entries tagged with this pass, in the order the
+        // device numbered them
+        const NewTok* ents = reinterpret_cast<const NewTok*>(hout + L.o_nt);
+        uint32_t k = 0;
+        while (k < kNewTokCap && ents[k].seq == S->nt_seq) ++k;
+        c.nt_met = k != 0;
+        bool ok = true;
+        for (uint32_t i = 0; i < m; ++i) ok &= c.st[i] == LASPJ_DEC_OK;
+        if (k && ok) c.newtoks.assign(ents, ents + k);
+        // (a merge's writer then wrote nothing and left the operands' cells)
+        if (k && c.op == Op::MERGE) S->clean_words = 0;
+    }
+    if (P.var_op)
+        for (int32_t x : c.st)
+            if (x != LASPJ_DEC_OK) S->clean_words = 0;   // (its cells were kept)
+    c.has_seg = false;
+    if (P.defer && cjob.armed &&
+        std::find(c.st.begin(), c.st.end(), (int32_t)LASPJ_DEC_UNKNOWN_TERM) != c.st.end()) {
+        // (the chain checks copied the failed payloads' results into the answer area;
+        // those of payloads that decoded are not read)
+        const EtfReadPlan& plan = P.plans[0];
+        c.segres.resize(8ull * plan.nseg);
+        std::memcpy(c.segres.data(), hout + L.o_seg, kSegResBytes * plan.nseg);
+        c.segbase = plan.segbase;
+        c.segS = plan.S;
+        c.has_seg = true;
+    }
+    c.res.assign(hout + L.o_res, hout + L.o_res + n);
+    if (P.has_payload_out) {
+        c.ooff.resize(n + 1ull);
+        std::memcpy(c.ooff.data(), hout + L.o_ooff, 8ull * (n + 1));
+        const uint64_t total = c.ooff[n];
+        if (total > L.ocap) {
+            // the writer wrote nothing: a larger answer area, the encode again
+            S->ocap = al(total + total / 4, 1 << 16);
+            return kPassAgain;
+        }
+        c.obase = hout + L.o_pay;
+    }
+    return LASPJ_OK;
+}
+
+// One device pass: plan, layout, fit, stage, pull, decode (or upload host-encoded cells),
+// answer, one synchronisation, collect.  Fills c.st / c.res / c.ooff / c.obase.
+//
+// What the phases must keep as it is:
+//   - for any call the same HIP operations reach ctx->stream in the same order (memsets,
+//     pulls, gathers, copies, kernels), and a pass synchronises exactly once;
+//   - ctx->mu (Guard) is held over fit_pass, over the waiters' payloads' gather inside
+//     stage_operands, and from pull_operands to the end — not over the rest of
+//     stage_operands (the offsets, the segment tables' copy into pinned memory, the host
+//     encoder): group-commit waiters queue their binds meanwhile;
+//   - S->clean_words says how many operand cells the enqueued kernels leave zero, set by
+//     the answer that decides it (and reset by collect_answers when a status says the
+//     cells were kept);
+//   - the nif_stats counters move where they did: ST_HOST_ENCODED per host-encoded pass,
+//     ST_PASSES and the timers ST_NS_ENQUEUE / _WAIT / _COPY at the synchronise,
+//     ST_NS_ANSWERS behind a pass that answered.
+int device_pass(laspj_ctx* ctx, NifState* S, Call& c) {
+    const uint64_t t0 = now_ns();
+    const PassPlan P = plan_pass(ctx, c);
+    const PassLayout L = layout_pass(S, c, P);
+    PassMem M;
+    if (int s = fit_pass(ctx, S, c, P, L, &M)) return s;
+    std::vector<int32_t> hst;       // the host encoder's statuses (no device decode)
+    if (int s = stage_operands(ctx, S, c, P, L, M, &hst)) return s;
+    Guard g(ctx);
+    uint64_t t_copy = 0;
+    ChainJob cjob;
+    if (int s = pull_operands(ctx, c, P, L, M, &t_copy)) return s;
+    if (int s = enqueue_decode(ctx, S, c, P, L, M, hst, &cjob)) return s;
+    if (int s = enqueue_answer(ctx, S, c, P, L, M, &cjob)) return s;
+    const uint64_t t1 = now_ns();
+    LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t t2 = now_ns();
+    ++S->stats[ST_PASSES];
+    S->stats[ST_NS_ENQUEUE] += t1 - t0;
+    S->stats[ST_NS_WAIT] += t2 - t1;
+    S->stats[ST_NS_COPY] += t_copy;
+    const int s = collect_answers(S, c, P, L, M, hst, cjob);
+    if (s == LASPJ_OK) S->stats[ST_NS_ANSWERS] += now_ns() - t2;
+    return s;
 }
 
 int register_payloads(laspj_ctx* ctx, NifState* S, KindState& K,
@@ -1453,8 +1641,8 @@ int register_payloads(laspj_ctx* ctx, NifState* S, KindState& K,
     st->assign(k, 0);
     if (int s = laspj_dict_add(K.dict, K.kind, blob.data(), offs.data(), k, -1, st->data()))
         return fail(ctx, s, "nif: dictionary registration failed (%d)", s);
-    ++S->stats[2];
-    S->stats[12] += now_ns() - t0;
+    ++S->stats[ST_REGISTRATIONS];
+    S->stats[ST_NS_REGISTER] += now_ns() - t0;
     K.stale = true;
     return LASPJ_OK;
 }
@@ -1485,15 +1673,13 @@ bool register_segments(NifState* S, const Call& c, const std::vector<uint32_t>& 
     if (rs.empty()) return false;
     for (const Range& r : rs) {
         // (the payload's group: its namespace's dictionary)
-        size_t g = 0;
-        while (g + 1 < c.groups.size() && r.i >= c.groups[g].p1) ++g;
-        KindState& K = *c.groups[g].K;
+        KindState& K = *c.groups[group_of(c, r.i)].K;
         if (dict_add_elems(K.dict, c.p[r.i], c.len[r.i], r.from, r.to) != LASPJ_DEC_OK)
             return false;       // (ranges already added stay: they hold well-formed terms)
         K.stale = true;
     }
-    ++S->stats[2];
-    S->stats[12] += now_ns() - t0;
+    ++S->stats[ST_REGISTRATIONS];
+    S->stats[ST_NS_REGISTER] += now_ns() - t0;
     return true;
 }
 
@@ -1550,9 +1736,9 @@ int register_new_tokens(laspj_ctx* ctx, NifState* S, KindState& K, const Call& c
     }
     dict_begin(K.dict);                           // (the journal kept nothing)
     K.stale = true;                               // (patched on the next call)
-    ++S->stats[2];
-    S->stats[18] += uniq.size();
-    S->stats[12] += now_ns() - t0;
+    ++S->stats[ST_REGISTRATIONS];
+    S->stats[ST_NEW_TOKENS] += uniq.size();
+    S->stats[ST_NS_REGISTER] += now_ns() - t0;
     return LASPJ_OK;
 }
 
@@ -1591,7 +1777,7 @@ int spill_vars(laspj_ctx* ctx, NifState* S, KindState& K) {
             release_cells(ctx, v);
         }
         v->resident = false;
-        ++S->stats[16];
+        ++S->stats[ST_SPILLED];
     }
     return LASPJ_OK;
 }
@@ -1609,7 +1795,7 @@ int reset_dict(laspj_ctx* ctx, NifState* S, KindState& K) {
     K.wide = false;                           // (a fresh dictionary starts narrow)
     K.tw = 1;
     ++K.epoch;
-    if (had) ++S->stats[3];
+    if (had) ++S->stats[ST_RESETS];
     return LASPJ_OK;
 }
 
@@ -1622,70 +1808,133 @@ bool widen(NifState* S, KindState& K, const std::vector<int32_t>& st) {
     return false;
 }
 
-// The call: device pass; operands with unknown terms registered and a second pass; every
-// other undecodable operand -> FALLBACK.  verdict[j] per answer.
-int run(laspj_ctx* ctx, NifState* S, Call& c, std::vector<int32_t>* verdict) {
-    ++S->stats[0];
-    const size_t G = c.groups.size();
-    for (const Group& g : c.groups)
-        if (!g.K->dict && reset_dict(ctx, S, *g.K)) return LASPJ_E_NOMEM;
-    const uint32_t n = c.n, m = c.m;
-    auto answer_of = [&](uint32_t i) { return i % n; };
-    auto group_of = [&](uint32_t i) {
-        size_t g = 0;
-        while (g + 1 < G && i >= c.groups[g].p1) ++g;
-        return g;
-    };
-    auto slice = [&](uint32_t p0, uint32_t p1, std::vector<const uint8_t*>* p,
-                     std::vector<uint64_t>* l) {
-        p->assign(c.p.begin() + p0, c.p.begin() + p1);
-        l->assign(c.len.begin() + p0, c.len.begin() + p1);
-    };
+// what run() keeps between a call's passes: the groups whose operands were registered, the
+// answers already given to the reference's clause
+struct RunState {
+    std::vector<uint8_t> registered;    // per group
+    std::vector<uint8_t> fallback;      // per answer (payload i belongs to answer i % n)
+};
+
+// a group's whole operands registered (again with a wide namespace when an element's 64
+// token slots ran out); the operands that did not register answer FALLBACK
+int register_group(laspj_ctx* ctx, NifState* S, const Call& c, size_t g, RunState* rs) {
+    KindState& K = *c.groups[g].K;
+    const uint32_t p0 = c.groups[g].p0, p1 = c.groups[g].p1;
+    const std::vector<const uint8_t*> rp(c.p.begin() + p0, c.p.begin() + p1);
+    const std::vector<uint64_t> rl(c.len.begin() + p0, c.len.begin() + p1);
+    std::vector<int32_t> rst;
+    if (int s = register_payloads(ctx, S, K, rp, rl, &rst)) return s;
+    if (widen(S, K, rst))
+        if (int s = register_payloads(ctx, S, K, rp, rl, &rst)) return s;
+    for (uint32_t i = p0; i < p1; ++i)
+        if (rst[i - p0] != LASPJ_DEC_OK) rs->fallback[i % c.n] = 1;
+    return LASPJ_OK;
+}
+
+// Ahead of a pass: every group's device images brought up to its dictionary (a group with
+// none yet registers its operands first), patched in place when only tokens were added.
+int refresh_images(laspj_ctx* ctx, NifState* S, Call& c, RunState* rs) {
+    for (size_t g = 0; g < c.groups.size(); ++g) {
+        KindState& K = *c.groups[g].K;
+        if (K.etf && !K.stale) continue;
+        if (!K.etf && c.groups[g].p1 > c.groups[g].p0) {
+            // nothing registered yet: register this group's operands first
+            if (int s = register_group(ctx, S, c, g, rs)) return s;
+            rs->registered[g] = 1;
+        }
+        // a wide namespace's operands are host-encoded: its device images serve the
+        // answers' writers only, so a call that writes none keeps the stale ones
+        // (while the cells' element slots and pairs still hold every term)
+        if (K.wide && K.etf && dict_elements(K.dict) <= K.E &&
+            dict_max_tokens(K.dict) <= 64u * K.tw && c.op != Op::MERGE &&
+            c.op != Op::VALUE && c.op != Op::VVALUE && c.op != Op::READ)
+            continue;
+        if (!patch_etf(ctx, S, K)) {
+            if (int s = rebuild_etf(ctx, S, K)) return s;
+            c.redo.n = 0;         // (element ranks moved: the last pass's results stale)
+        }
+    }
+    return LASPJ_OK;
+}
+
+// Terms a dictionary has not seen (or operands that are not orddicts, which the next pass
+// tells apart): each group registers its operands that met them (an operand that decoded
+// holds only registered terms).
+int register_unknown(laspj_ctx* ctx, NifState* S, Call& c, const std::vector<uint32_t>& unknown,
+                     RunState* rs) {
     // a variable call's operands are its own (payload i belongs to variable i): an element
     // past its 64 token slots widens the namespace's cells (k {p, r} pairs); only image
     // calls start a fresh dictionary for it, and only write/4 resets a dictionary grown past
     // its bound (bind / threshold answer FALLBACK there and the NIF runs the reference's
     // clause over the variable's read image)
     const bool may_reset = !(c.op == Op::BIND || c.op == Op::THRESHOLD);
-    std::vector<uint8_t> fallback(n, 0);
-    std::vector<uint8_t> registered(G, 0);
+    for (size_t g = 0; g < c.groups.size(); ++g) {
+        KindState& K = *c.groups[g].K;
+        const uint32_t p0 = c.groups[g].p0, p1 = c.groups[g].p1;
+        std::vector<uint32_t> ri;
+        std::vector<const uint8_t*> rp;
+        std::vector<uint64_t> rl;
+        std::vector<int32_t> rst;
+        for (uint32_t i : unknown)
+            if (i >= p0 && i < p1) {
+                rp.push_back(c.p[i]);
+                rl.push_back(c.len[i]);
+                ri.push_back(i);
+            }
+        if (ri.empty()) continue;
+        uint32_t nd = 0;
+        uint64_t eb, tb;
+        if (int s = register_payloads(ctx, S, K, rp, rl, &rst)) return s;
+        bool full = false;
+        for (int32_t x : rst) full |= x == LASPJ_DEC_UNREPRESENTABLE;
+        laspj_dict_info(K.dict, &nd, &eb, &tb);
+        // image calls own their namespace's terms for the call only: a wide one starts
+        // over narrow when it meets new terms (the narrow codec is the fast one)
+        const bool image_call = c.vars.empty();
+        if (may_reset && ((image_call && ((full && nd) || K.wide)) || nd > kMaxDictElements)) {
+            // an element's 64 token slots used up by earlier calls (or a dictionary grown
+            // past its bound): start a fresh dictionary holding this group's terms only —
+            // image calls are self-contained (images in, images out); the namespace's
+            // resident variables are written out to their images first and decoded again
+            // when next used
+            // (an operand of more than 64 tokens on an element even so: wide)
+            if (int s = reset_dict(ctx, S, K)) return s;
+            if (int s = register_group(ctx, S, c, g, rs)) return s;
+            for (uint32_t i = p0; i < p1 && i < c.vars.size(); ++i) {
+                c.vars[i]->epoch = K.epoch;           // write/4's own variable: new cells
+                c.vars[i]->resident = true;
+            }
+        } else {
+            // a variable's namespace (its replicas' cells hold its slots) goes wide
+            // rather than start over
+            if (widen(S, K, rst))
+                if (int s = register_payloads(ctx, S, K, rp, rl, &rst)) return s;
+            for (size_t k = 0; k < ri.size(); ++k)
+                if (rst[k] != LASPJ_DEC_OK) rs->fallback[ri[k] % c.n] = 1;
+        }
+        rs->registered[g] = 1;
+    }
+    return LASPJ_OK;
+}
+
+// The call: device pass; operands with unknown terms registered and a second pass; every
+// other undecodable operand -> FALLBACK.  verdict[j] per answer.
+int run(laspj_ctx* ctx, NifState* S, Call& c, std::vector<int32_t>* verdict) {
+    ++S->stats[ST_CALLS];
+    const size_t G = c.groups.size();
+    for (const Group& g : c.groups)
+        if (!g.K->dict && reset_dict(ctx, S, *g.K)) return LASPJ_E_NOMEM;
+    const uint32_t n = c.n, m = c.m;
+    RunState rs{std::vector<uint8_t>(G, 0), std::vector<uint8_t>(n, 0)};
     bool partial = false;           // the last registration took the failing segments only
     bool resolved = false;          // the last pass's answers stand (statuses all final)
     const int passes = ctx->tune_nif_passes ? (int)ctx->tune_nif_passes : kMaxPasses;
-    std::vector<const uint8_t*> rp;
-    std::vector<uint64_t> rl;
-    std::vector<int32_t> rst;
     std::vector<uint8_t> written;
     for (int pass = 0; pass < passes && !resolved; ++pass) {
-        for (size_t g = 0; g < G; ++g) {
-            KindState& K = *c.groups[g].K;
-            if (K.etf && !K.stale) continue;
-            const uint32_t p0 = c.groups[g].p0, p1 = c.groups[g].p1;
-            if (!K.etf && p1 > p0) {
-                // nothing registered yet: register this group's operands first
-                slice(p0, p1, &rp, &rl);
-                if (int s = register_payloads(ctx, S, K, rp, rl, &rst)) return s;
-                if (widen(S, K, rst))
-                    if (int s = register_payloads(ctx, S, K, rp, rl, &rst)) return s;
-                registered[g] = 1;
-                for (uint32_t i = p0; i < p1; ++i)
-                    if (rst[i - p0] != LASPJ_DEC_OK) fallback[answer_of(i)] = 1;
-            }
-            // a wide namespace's operands are host-encoded: its device images serve the
-            // answers' writers only, so a call that writes none keeps the stale ones
-            // (while the cells' element slots and pairs still hold every term)
-            if (K.wide && K.etf && dict_elements(K.dict) <= K.E &&
-                dict_max_tokens(K.dict) <= 64u * K.tw && c.op != Op::MERGE &&
-                c.op != Op::VALUE && c.op != Op::VVALUE && c.op != Op::READ)
-                continue;
-            if (!patch_etf(ctx, S, K)) {
-                if (int s = rebuild_etf(ctx, S, K)) return s;
-                c.redo.n = 0;         // (element ranks moved: the last pass's results stale)
-            }
-        }
+        if (int s = refresh_images(ctx, S, c, &rs)) return s;
         int s = device_pass(ctx, S, c);
         c.redo.n = 0;                 // (a redo pass is taken once)
-        if (s == -1000) {
+        if (s == kPassAgain) {
             // answer area grown: once more (a write-only pass's writer may have cleared
             // the operands: decode them again)
             if (c.write_only) {
@@ -1732,34 +1981,34 @@ int run(laspj_ctx* ctx, NifState* S, Call& c, std::vector<int32_t>* verdict) {
             // a segment chain that only a serial decode can judge: once more, decoding
             // serially (the join's answer of this pass is not used)
             c.no_defer = true;
-            ++S->stats[15];
+            ++S->stats[ST_CHAIN_REDOS];
             continue;
         }
         std::vector<uint32_t> unknown;
         for (uint32_t i = 0; i < m; ++i) {
-            if (fallback[answer_of(i)]) continue;
+            if (rs.fallback[i % n]) continue;
             // (an element past a narrow namespace's 64 token slots: its registration widens
             // the namespace)
-            const KindState& Ki = *c.groups[group_of(i)].K;
+            const KindState& Ki = *c.groups[group_of(c, i)].K;
             const bool grow = c.st[i] == LASPJ_DEC_UNREPRESENTABLE &&
                               Ki.kind == LASPJ_KIND_ORSET && !Ki.wide;
             if ((c.st[i] == LASPJ_DEC_UNKNOWN_TERM || grow) &&
-                (!registered[group_of(i)] || partial))
+                (!rs.registered[group_of(c, i)] || partial))
                 unknown.push_back(i);
             else if (c.st[i] != LASPJ_DEC_OK)
-                fallback[answer_of(i)] = 1;
+                rs.fallback[i % n] = 1;
         }
         if (unknown.empty()) {
             resolved = true;
             break;
         }
         bool fresh = true;            // no group of an unknown operand registered yet
-        for (uint32_t i : unknown) fresh &= !registered[group_of(i)];
+        for (uint32_t i : unknown) fresh &= !rs.registered[group_of(c, i)];
         if (fresh && c.has_seg && register_segments(S, c, unknown)) {
             // the failing segments' elements registered; if the next pass still meets an
             // unknown term, the whole operands are registered after all
             partial = true;
-            for (uint32_t i : unknown) registered[group_of(i)] = 1;
+            for (uint32_t i : unknown) rs.registered[group_of(c, i)] = 1;
             // a single bind: the next pass decodes only those segments again, over the
             // payload and cells this pass left (when the images are patched, not rebuilt)
             if (c.op == Op::BIND && n == 1 && !c.no_defer && !c.nt_met) {
@@ -1775,59 +2024,7 @@ int run(laspj_ctx* ctx, NifState* S, Call& c, std::vector<int32_t>* verdict) {
             continue;
         }
         partial = false;
-        // terms a dictionary has not seen (or operands that are not orddicts, which the
-        // second pass tells apart): each group registers its operands that met them (an
-        // operand that decoded holds only registered terms)
-        for (size_t g = 0; g < G; ++g) {
-            KindState& K = *c.groups[g].K;
-            const uint32_t p0 = c.groups[g].p0, p1 = c.groups[g].p1;
-            std::vector<uint32_t> ri;
-            rp.clear();
-            rl.clear();
-            for (uint32_t i : unknown)
-                if (i >= p0 && i < p1) {
-                    rp.push_back(c.p[i]);
-                    rl.push_back(c.len[i]);
-                    ri.push_back(i);
-                }
-            if (ri.empty()) continue;
-            uint32_t nd = 0;
-            uint64_t eb, tb;
-            if (int s2 = register_payloads(ctx, S, K, rp, rl, &rst)) return s2;
-            bool full = false;
-            for (int32_t x : rst) full |= x == LASPJ_DEC_UNREPRESENTABLE;
-            laspj_dict_info(K.dict, &nd, &eb, &tb);
-            // image calls own their namespace's terms for the call only: a wide one starts
-            // over narrow when it meets new terms (the narrow codec is the fast one)
-            const bool image_call = c.vars.empty();
-            if (may_reset && ((image_call && ((full && nd) || K.wide)) || nd > kMaxDictElements)) {
-                // an element's 64 token slots used up by earlier calls (or a dictionary grown
-                // past its bound): start a fresh dictionary holding this group's terms only —
-                // image calls are self-contained (images in, images out); the namespace's
-                // resident variables are written out to their images first and decoded again
-                // when next used
-                if (int s2 = reset_dict(ctx, S, K)) return s2;
-                slice(p0, p1, &rp, &rl);
-                if (int s2 = register_payloads(ctx, S, K, rp, rl, &rst)) return s2;
-                // (an operand of more than 64 tokens on an element even so: wide)
-                if (widen(S, K, rst))
-                    if (int s2 = register_payloads(ctx, S, K, rp, rl, &rst)) return s2;
-                for (uint32_t i = p0; i < p1; ++i)
-                    if (rst[i - p0] != LASPJ_DEC_OK) fallback[answer_of(i)] = 1;
-                for (uint32_t i = p0; i < p1 && i < c.vars.size(); ++i) {
-                    c.vars[i]->epoch = K.epoch;           // write/4's own variable: new cells
-                    c.vars[i]->resident = true;
-                }
-            } else {
-                // a variable's namespace (its replicas' cells hold its slots) goes wide
-                // rather than start over
-                if (widen(S, K, rst))
-                    if (int s2 = register_payloads(ctx, S, K, rp, rl, &rst)) return s2;
-                for (size_t k = 0; k < ri.size(); ++k)
-                    if (rst[k] != LASPJ_DEC_OK) fallback[answer_of(ri[k])] = 1;
-            }
-            registered[g] = 1;
-        }
+        if (int s2 = register_unknown(ctx, S, c, unknown, &rs)) return s2;
     }
     // post-condition: an answer is OK only from a pass whose statuses were all final; a
     // call whose passes ran out (the answer area grown, a segment chain only a serial
@@ -1836,9 +2033,9 @@ int run(laspj_ctx* ctx, NifState* S, Call& c, std::vector<int32_t>* verdict) {
     if (c.op == Op::BIND && written.size() == n) c.res = written;
     verdict->assign(n, LASPJ_NIF_OK);
     for (uint32_t j = 0; j < n; ++j)
-        if (fallback[j] || !resolved) {
+        if (rs.fallback[j] || !resolved) {
             (*verdict)[j] = LASPJ_NIF_FALLBACK;
-            ++S->stats[6];
+            ++S->stats[ST_FALLBACKS];
         }
     return LASPJ_OK;
 }
@@ -1885,7 +2082,7 @@ int hydrate(laspj_ctx* ctx, NifState* S, laspj_var* v, bool* ok) {
         v->image.clear();
         v->image.shrink_to_fit();
         *ok = true;
-        ++S->stats[17];
+        ++S->stats[ST_HYDRATED];
         return LASPJ_OK;
     }
     // (a reset inside the call may have written the empty cells out over the image)
@@ -1906,7 +2103,7 @@ int hydrate(laspj_ctx* ctx, NifState* S, laspj_var* v, bool* ok) {
 // variable has a waiter to check.
 int recheck_pass(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_var* const* vars,
                  int32_t* verdict, std::vector<std::vector<uint8_t>>* met) {
-    ++S->stats[0];
+    ++S->stats[ST_CALLS];
     met->assign(n, {});
     std::vector<uint32_t> live;
     uint32_t nws = 0;
@@ -1928,7 +2125,7 @@ int recheck_pass(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_var* const* vars
         for (const Waiter& w : v->waiters) ok = ok && current(w.cells);
         verdict[i] = ok ? LASPJ_NIF_OK : LASPJ_NIF_FALLBACK;
         if (!ok) {
-            ++S->stats[6];
+            ++S->stats[ST_FALLBACKS];
         } else if (!v->waiters.empty()) {
             live.push_back(i);
             nws += (uint32_t)v->waiters.size();
@@ -1938,24 +2135,12 @@ int recheck_pass(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_var* const* vars
     const uint64_t t0 = now_ns();
     const uint32_t nv = (uint32_t)live.size();
     // in region (pinned, read by the kernel in place): [WaitVar x nv | WaitDesc x nws];
-    // device words: [ticket, 16 bytes | {flags, np} x nws | nc x nv]; answers: nws bytes
+    // device words: [{flags, np} x nws | nc x nv]; answers: nws bytes
     const uint64_t i_ws = 32ull * nv, in_bytes = i_ws + 16ull * nws;
-    const uint64_t z_rec = 16, z_nc = z_rec + 8ull * nws, z_bytes = al(z_nc + 4ull * nv, 16);
+    const uint64_t z_nc = 8ull * nws, z_bytes = al(z_nc + 4ull * nv, 16);
     Guard g(ctx);
     if (int s = grow_dev(ctx, &S->dblk, &S->dblk_bytes, z_bytes)) return s;
-    if (int s = grow_host(ctx, &S->hin, &S->hin_bytes, in_bytes)) return s;
-    if (int s = grow_host(ctx, &S->hout, &S->hout_bytes, nws)) return s;
-    void* hd = nullptr;
-    if (S->hin_dkey != S->hin) {
-        LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hin, 0));
-        S->hin_d = static_cast<uint8_t*>(hd);
-        S->hin_dkey = S->hin;
-    }
-    if (S->hout_dkey != S->hout) {
-        LJ_HIP(ctx, hipHostGetDevicePointer(&hd, S->hout, 0));
-        S->hout_d = static_cast<uint8_t*>(hd);
-        S->hout_dkey = S->hout;
-    }
+    if (int s = fit_staging(ctx, S, in_bytes, nws)) return s;
     auto* hv = reinterpret_cast<WaitVar*>(S->hin);
     auto* hw = reinterpret_cast<WaitDesc*>(static_cast<uint8_t*>(S->hin) + i_ws);
     uint64_t items = 0;
@@ -1991,32 +2176,25 @@ int recheck_pass(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_var* const* vars
         w0 += nw;
     }
     uint8_t* dz = static_cast<uint8_t*>(S->dblk);
-    auto* ticket = reinterpret_cast<uint32_t*>(dz);
-    auto* rec = reinterpret_cast<uint32_t*>(dz + z_rec);
+    auto* rec = reinterpret_cast<uint32_t*>(dz);
     auto* nc = reinterpret_cast<uint32_t*>(dz + z_nc);
     const auto* dv = reinterpret_cast<const WaitVar*>(S->hin_d);
     const auto* dw = reinterpret_cast<const WaitDesc*>(S->hin_d + i_ws);
     LJ_HIP(ctx, hipMemsetAsync(dz, 0, z_bytes, ctx->stream));
     const unsigned grid = (unsigned)std::max<uint64_t>(
         1, std::min<uint64_t>((items + 3) / 4, (uint64_t)ctx->cus * 8));
-    if (ctx->tune_waiter_finish == 2) {
-        hipLaunchKernelGGL(k_waiter_check<true>, dim3(grid), dim3(256), 0, ctx->stream, dv, nv, dw,
-                           nws, items, ticket, rec, nc, S->hout_d);
-        LJ_LAUNCHED(ctx);
-    } else {
-        hipLaunchKernelGGL(k_waiter_check<false>, dim3(grid), dim3(256), 0, ctx->stream, dv, nv,
-                           dw, nws, items, ticket, rec, nc, S->hout_d);
-        LJ_LAUNCHED(ctx);
-        hipLaunchKernelGGL(k_waiter_finish, dim3(1), dim3(256), 0, ctx->stream, dv, dw, nws, rec,
-                           nc, S->hout_d);
-        LJ_LAUNCHED(ctx);
-    }
+    hipLaunchKernelGGL(k_waiter_check, dim3(grid), dim3(256), 0, ctx->stream, dv, nv, dw, items,
+                       rec, nc);
+    LJ_LAUNCHED(ctx);
+    hipLaunchKernelGGL(k_waiter_finish, dim3(1), dim3(256), 0, ctx->stream, dv, dw, nws, rec, nc,
+                       S->hout_d);
+    LJ_LAUNCHED(ctx);
     const uint64_t t1 = now_ns();
     LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t t2 = now_ns();
-    ++S->stats[1];
-    S->stats[8] += t1 - t0;
-    S->stats[9] += t2 - t1;
+    ++S->stats[ST_PASSES];
+    S->stats[ST_NS_ENQUEUE] += t1 - t0;
+    S->stats[ST_NS_WAIT] += t2 - t1;
     const uint8_t* hout = static_cast<const uint8_t*>(S->hout);
     w0 = 0;
     for (uint32_t a = 0; a < nv; ++a) {
@@ -2024,7 +2202,7 @@ int recheck_pass(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_var* const* vars
         (*met)[live[a]].assign(hout + w0, hout + w0 + nw);
         w0 += nw;
     }
-    S->stats[10] += now_ns() - t2;
+    S->stats[ST_NS_ANSWERS] += now_ns() - t2;
     return LASPJ_OK;
 }
 
@@ -2761,7 +2939,7 @@ int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int str
     *met = 0;
     *verdict = LASPJ_NIF_FALLBACK;
     if (!ok) {
-        ++S->stats[6];
+        ++S->stats[laspj::ST_FALLBACKS];
         return LASPJ_OK;
     }
     // threshold_met(Type, Value, Threshold) (lasp_lattice.erl:62-75) as
@@ -2936,21 +3114,21 @@ int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
     std::lock_guard<std::mutex> lk(S->mu);
     if (!S->vars.count(out) || !S->vars.count(l) || !S->vars.count(r))
         return fail(ctx, LASPJ_E_INVAL, "var_union: unknown variable");
-    ++S->stats[0];
+    ++S->stats[laspj::ST_CALLS];
     *status = LASPJ_BIND_NOOP;
     *verdict = LASPJ_NIF_FALLBACK;
     // OR-Sets of one namespace only: a G-Set's body is `LValue ++ RValue` (a list value),
     // and cells of two namespaces name different terms by one slot
     if (out->kind != LASPJ_KIND_ORSET || l->kind != LASPJ_KIND_ORSET ||
         r->kind != LASPJ_KIND_ORSET || l->ns != out->ns || r->ns != out->ns) {
-        ++S->stats[6];
+        ++S->stats[laspj::ST_FALLBACKS];
         return LASPJ_OK;
     }
     for (laspj_var* v : {out, l, r}) {
         bool ok = false;
         if (int s = laspj::hydrate(ctx, S, v, &ok)) return s;
         if (!ok) {
-            ++S->stats[6];
+            ++S->stats[laspj::ST_FALLBACKS];
             return LASPJ_OK;
         }
     }
@@ -2997,7 +3175,7 @@ int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_
         return fail(ctx, LASPJ_E_INVAL, "var_update: null argument");
     std::lock_guard<std::mutex> lk(S->mu);
     if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_update: unknown variable");
-    ++S->stats[0];
+    ++S->stats[laspj::ST_CALLS];
     *result = LASPJ_UPDATE_OK;
     *verdict = LASPJ_NIF_FALLBACK;
     if (err_elem) *err_elem = nullptr;
@@ -3007,7 +3185,7 @@ int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_
     bool ok = false;
     if (int s = laspj::hydrate(ctx, S, var, &ok)) return s;
     auto fallback = [&] {
-        ++S->stats[6];
+        ++S->stats[laspj::ST_FALLBACKS];
         return LASPJ_OK;
     };
     if (!ok) return fallback();
@@ -3105,10 +3283,10 @@ int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_
     laspj::dict_begin(K.dict);                    // (the journal kept nothing)
     registered |= laspj::dict_elements(K.dict) != nd0;
     if (registered) {
-        ++S->stats[2];
+        ++S->stats[laspj::ST_REGISTRATIONS];
         K.stale = true;
     }
-    S->stats[12] += laspj::now_ns() - t0;
+    S->stats[laspj::ST_NS_REGISTER] += laspj::now_ns() - t0;
     // the device images learn the new terms before the namespace's next device pass: a
     // token on a known element is patched in by that pass (run() patches a stale namespace
     // first — consecutive updates batch their patches); new elements or a new width need

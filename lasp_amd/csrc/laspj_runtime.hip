@@ -353,8 +353,10 @@ int laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value) {
             ctx->tune_etf = value;
             return LASPJ_OK;
         case LASPJ_TUNE_ETF_READ:
-            if (value < 0 || value > 15 || value == 9)
-                return fail(ctx, LASPJ_E_INVAL, "tuning: etf read must be 0..8 or 10..15");
+            // (3, 5, 8 and 9 named forms that lost their measurement and were deleted)
+            if (value < 0 || value > 15 || value == 3 || value == 5 || value == 8 || value == 9)
+                return fail(ctx, LASPJ_E_INVAL,
+                            "tuning: etf read must be 0, 1, 2, 4, 6, 7 or 10..15");
             ctx->tune_etf_read = value;
             return LASPJ_OK;
         case LASPJ_TUNE_ETF_SEG:
@@ -376,12 +378,6 @@ int laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value) {
                 return fail(ctx, LASPJ_E_INVAL, "tuning: list chunk 0 or 64 .. 2^20");
             ctx->tune_list_chunk = value;
             return LASPJ_OK;
-        case LASPJ_TUNE_WAITER_FINISH:
-            if (value < 0 || value > 2)
-                return fail(ctx, LASPJ_E_INVAL, "tuning: waiter finish 0 .. 2");
-            ctx->tune_waiter_finish = value;
-            return LASPJ_OK;
-
         default:
             return fail(ctx, LASPJ_E_INVAL, "tuning: unknown knob %d", knob);
     }

@@ -230,6 +230,29 @@ def test_var_gset_bind_read_threshold():
         ctx.close()
 
 
+def test_var_read_regrows_the_answer_area():
+    """A value whose image is just over the 1 MiB the answer area starts at (2200 ascending
+    480-byte binaries: 1 + 1 + 4 + 2200 * 485 + 1 bytes): the first read's writer finds the
+    area short and writes nothing, the area is grown and the pass taken again — two device
+    passes — and the read answers the oracle's image; the next read fits in one."""
+    ctx = _ctx()
+    try:
+        elems = otp.lists_usort([k.to_bytes(4, "big") + b"r" * 476 for k in range(2200)])
+        img = _tb(elems)
+        assert len(img) == 1 + 1 + 4 + 2200 * 485 + 1 and len(img) > 1 << 20
+        var = ctx.var("gset")
+        assert var.write(img) == OK
+        p0 = ctx.nif_stats()["device_passes"]
+        assert var.read() == (OK, img)
+        p1 = ctx.nif_stats()["device_passes"]
+        assert p1 - p0 == 2
+        assert var.read() == (OK, img)
+        assert ctx.nif_stats()["device_passes"] - p1 == 1
+        var.close()
+    finally:
+        ctx.close()
+
+
 def test_var_bind_many_and_fallbacks():
     """Eight variables bound in one device pass (laspj_var_etf_bind_many); an operand the
     columnar form does not take answers FALLBACK and leaves its variable as it was; a

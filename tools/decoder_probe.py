@@ -22,7 +22,7 @@ R, E, T = 4096, 1024, 64
 KS = [int(k) for k in os.environ.get("KS", "4,16,32,48,64").split(",")]
 STEPS = int(os.environ.get("STEPS", "10"))
 SEGS = [int(x) for x in os.environ.get("SEGS", "0").split(",")]   # LASPJ_TUNE_ETF_SEG values
-# LASPJ_TUNE_ETF_READ values to A/B (0: the item decoder at this shape, 8: the wave decoder)
+# LASPJ_TUNE_ETF_READ values to A/B (0: the default decoders, 2: records without element batches)
 READS = [int(x) for x in os.environ.get("READS", "0").split(",")]
 
 ctx = engine.Context(0)

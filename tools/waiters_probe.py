@@ -5,9 +5,7 @@ the `steady` leg's shape: a 10k-element OR-Set variable and W waiters with disti
 way) or (b) one laspj_var_recheck over the waiters kept on the device; then
 laspj_var_recheck_many over 32 variables x 16 waiters after a bind_many.  One JSON line:
 medians in microseconds and the host-time split of laspj_nif_stats per device pass ([8]
-stage + enqueue, [9] device wait, [10] answers, [13] image patch), for W in {1, 16, 64} and
-both finishes of the re-check (LASPJ_TUNE_WAITER_FINISH 1: finish launch, 2: last-arriving
-block).
+stage + enqueue, [9] device wait, [10] answers, [13] image patch), for W in {1, 16, 64}.
 
     python tools/waiters_probe.py [steps]
 """
@@ -51,7 +49,7 @@ def split(ctx, s0, calls):
     return {k: round(v, 2) for k, v in d.items()}
 
 
-def one_variable(ctx, img0, w, steps, finishes):
+def one_variable(ctx, img0, w, steps):
     L = ctx.L
     res, vd, nm = C.c_int32(), C.c_int32(), C.c_uint32()
     ei, el, mi = C.c_void_p(), C.c_uint64(), C.c_void_p()
@@ -92,33 +90,29 @@ def one_variable(ctx, img0, w, steps, finishes):
     out["threshold_split_us_per_call"] = split(ctx, s0, steps * w)
     var.close()
     # (b) one re-check of the waiters kept on the device
-    for fin in finishes:
-        ctx.set_tuning(_lib.TUNE_WAITER_FINISH, fin)
-        var = ctx.var("orset")
-        var.write(img0)
-        for k, th in enumerate(ths):
-            if var.wait(th, False, k) != (0, False):
-                raise RuntimeError("probe: wait answered wrongly")
-        ids = (C.c_uint64 * w)()
-        nmet, left = C.c_uint32(), C.c_uint32()
-        ts = []
-        for k in range(steps + 20):
-            if k == 20:
-                s0 = ctx.nif_stats()
-            update(var, k)
-            t0 = time.perf_counter()
-            check(L.laspj_var_recheck(var.h, ids, w, C.byref(nmet), C.byref(left), C.byref(vd)),
-                  ctx.h)
-            dt = time.perf_counter() - t0
-            if vd.value != 0 or nmet.value != 0 or left.value != w:
-                raise RuntimeError("probe: recheck answered wrongly")
-            if k >= 20:
-                ts.append(dt * 1e6)
-        name = {1: "finish_launch", 2: "last_block"}[fin]
-        out[f"us_recheck_median_{name}"] = round(statistics.median(ts), 2)
-        out[f"recheck_split_us_{name}"] = split(ctx, s0, steps)
-        var.close()
-    ctx.set_tuning(_lib.TUNE_WAITER_FINISH, 0)
+    var = ctx.var("orset")
+    var.write(img0)
+    for k, th in enumerate(ths):
+        if var.wait(th, False, k) != (0, False):
+            raise RuntimeError("probe: wait answered wrongly")
+    ids = (C.c_uint64 * w)()
+    nmet, left = C.c_uint32(), C.c_uint32()
+    ts = []
+    for k in range(steps + 20):
+        if k == 20:
+            s0 = ctx.nif_stats()
+        update(var, k)
+        t0 = time.perf_counter()
+        check(L.laspj_var_recheck(var.h, ids, w, C.byref(nmet), C.byref(left), C.byref(vd)),
+              ctx.h)
+        dt = time.perf_counter() - t0
+        if vd.value != 0 or nmet.value != 0 or left.value != w:
+            raise RuntimeError("probe: recheck answered wrongly")
+        if k >= 20:
+            ts.append(dt * 1e6)
+    out["us_recheck_median"] = round(statistics.median(ts), 2)
+    out["recheck_split_us"] = split(ctx, s0, steps)
+    var.close()
     return out
 
 
@@ -163,10 +157,10 @@ def main():
     img0 = etf.term_to_binary([(e, [(tok(b"A", e), False)]) for e in range(N)])
     imgb = etf.term_to_binary([(e, [(tok(b"B", e), e % 10 == 0)]) for e in range(N)])
     out = {"shape": f"{N}-element OR-Set variable, 50-element thresholds, {steps} steps",
-           "one_variable": [one_variable(ctx, img0, w, steps, (1, 2)) for w in (1, 16, 64)],
+           "one_variable": [one_variable(ctx, img0, w, steps) for w in (1, 16, 64)],
            "recheck_many": many(ctx, img0, imgb, 10)}
     r16 = out["one_variable"][1]
-    best = r16["us_recheck_median_finish_launch"]          # the default finish
+    best = r16["us_recheck_median"]
     out["gate_w16"] = {
         "us_recheck": best, "us_one_threshold_call": r16["us_threshold_call_median"],
         "recheck_le_one_threshold_call": best <= r16["us_threshold_call_median"],
