@@ -823,6 +823,34 @@ int laspj_dict_export(const laspj_dict* dict, uint32_t E, uint8_t* elem_blob, ui
 int laspj_dict_encode(const laspj_dict* dict, int32_t kind, const uint8_t* blob,
                       const uint64_t* offsets, uint64_t n, int tag, uint32_t E, uint64_t* out,
                       int32_t* status);
+/* riak_dt_gcounter's state, the orddict [{Actor, Count}] (include/lasp.hrl:76), between its
+ * term_to_binary/1 image and {slot, count} pairs over a dictionary of actor terms (element
+ * terms only).  parse: the image (131 + the list) walked in list order, unseen actors
+ * registered; *status LASPJ_DEC_OK and the pairs written, or not OK — not a proper list of
+ * 2-tuples, actors not strictly ascending in term order, a Count that is not an integer in
+ * 1 .. 2^64 - 1 (any ETF integer encoding), an Actor `==` to a registered term under another
+ * image (LASPJ_DEC_EQUAL_TERMS), more than 2^20 actors, a truncated image — with every
+ * registration of the call undone and *npairs 0.  More pairs than cap: LASPJ_E_RANGE with
+ * *npairs the room to come back with (the registrations stay). */
+int laspj_gcounter_etf_parse(laspj_dict* dict, const uint8_t* image, uint64_t n, uint32_t* slots,
+                             uint64_t* counts, uint32_t cap, uint32_t* npairs, int32_t* status);
+/* pairs in term order of their actors -> the image term_to_binary/1 writes (integers as
+ * SMALL_INTEGER_EXT / INTEGER_EXT / SMALL_BIG_EXT; zero counts are absent actors and are
+ * skipped); *out_len > cap: LASPJ_E_RANGE, nothing written */
+int laspj_gcounter_etf_encode(const laspj_dict* dict, const uint32_t* slots,
+                              const uint64_t* counts, uint32_t npairs, uint8_t* out, uint64_t cap,
+                              uint64_t* out_len);
+#define LASPJ_GC_NEVER  0
+#define LASPJ_GC_ALWAYS 1
+#define LASPJ_GC_T      2
+/* threshold_met(riak_dt_gcounter, V, T) (lasp_lattice.erl:87-90: `T =< value(V)`, strict:
+ * `T < value(V)`, in term order) planned from T's image: *plan LASPJ_GC_NEVER (a
+ * non-number is above every number; t >= 2^64), LASPJ_GC_ALWAYS (t =< 0) or LASPJ_GC_T with
+ * *t, met iff `*t =< value(V)` — t = T (strict: T + 1) for an integer, ceil(T) (strict:
+ * floor(T) + 1) for a float, compared exactly (laspj_term_compare).  LASPJ_E_INVAL: the
+ * image is not one term. */
+int laspj_gcounter_threshold_plan(const uint8_t* threshold, uint64_t n, int strict, int32_t* plan,
+                                  uint64_t* t);
 
 /* ------------------------------------------------------------------ NIF entry points */
 /* What a NIF function does between enif_term_to_binary/3 and enif_binary_to_term/4, as
@@ -920,10 +948,20 @@ int laspj_gset_etf_inflation(laspj_ctx* ctx, const uint8_t* prev, uint64_t np,
  * bind / update / threshold / value answer FALLBACK — the NIF runs the reference's clause
  * over the read term and stores the outcome with laspj_var_etf_write.  A namespace whose
  * dictionary grows past 2^20 elements starts a fresh one on write/4 and writes its
- * resident variables out to their images first; each is decoded again on its next call. */
+ * resident variables out to their images first; each is decoded again on its next call.
+ *
+ * LASPJ_KIND_GCOUNTER: a riak_dt_gcounter variable (include/lasp.hrl:76; the advertisement
+ * counter's type, riak_test/lasp_adcounter_test.erl) is one row of uint64 counts over the
+ * actor slots of its namespace, 0 = absent; the row's capacity doubles as actors arrive,
+ * each replica's on its own.  Its images are walked on the host
+ * (laspj_gcounter_etf_parse) and only {slot, count} pairs reach the device; every call is
+ * one launch and one synchronisation.  Not representable — verdict FALLBACK of bind /
+ * threshold / wait / increment with the variable unchanged, the image held on the host by
+ * write — is an image laspj_gcounter_etf_parse refuses.  Sums wrap at 2^64, as the batch
+ * path's (laspj_gcounter_values). */
 typedef struct laspj_var laspj_var;
 /* declare/3 (lasp_core.erl:208-218): a variable holding Type:new() = [] (kind
- * LASPJ_KIND_ORSET or LASPJ_KIND_GSET), in a namespace of its own */
+ * LASPJ_KIND_ORSET, LASPJ_KIND_GSET or LASPJ_KIND_GCOUNTER), in a namespace of its own */
 int laspj_var_create(laspj_ctx* ctx, int32_t kind, laspj_var** out);
 /* another replica of `peer`'s variable (its kind, context and namespace), holding new() */
 int laspj_var_create_replica(laspj_var* peer, laspj_var** out);
@@ -936,25 +974,35 @@ int laspj_var_destroy(laspj_var* var);
  * unchanged and the NIF binds in Erlang (as above).  Calls arriving on one context while a
  * device pass runs are served together by the next pass (group commit, as bind_many);
  * while it waits, a caller copies its own image (64 KiB or more) into a pinned block the
- * pass gathers from, so `value` must stay valid until the call returns, as always. */
+ * pass gathers from, so `value` must stay valid until the call returns, as always.
+ * A counter (lasp_core.erl:291-312 with riak_dt_gcounter:merge/2): NOOP iff the actor sets
+ * and counts are the same, else the row := the per-actor max and WRITTEN (also when the
+ * max leaves the row as it was: the reference writes then too); it takes the context's call
+ * lock directly, never the group-commit queue. */
 int laspj_var_etf_bind(laspj_var* var, const uint8_t* value, uint64_t n, int32_t* status,
                        int32_t* verdict);
 /* n binds (lasp_core.erl:291-312) of distinct variables of one kind and context in one
- * device pass (a vnode's queued binds, lasp_vnode.erl:213-237) */
+ * device pass (a vnode's queued binds, lasp_vnode.erl:213-237).  Counters (of any
+ * namespaces): one launch and one synchronisation; counters and sets in one call:
+ * LASPJ_E_KIND */
 int laspj_var_etf_bind_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars,
                             const uint8_t* const* values, const uint64_t* lens, int32_t* status,
                             int32_t* verdict);
 /* write/4 (lasp_core.erl:839-844): the variable := value (verdict FALLBACK: held as the
- * image on the host) */
+ * image on the host); a counter's row := the image's counts */
 int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_t* verdict);
-/* #dv.value as term_to_binary/1 (*out valid until the context's next call) */
+/* #dv.value as term_to_binary/1 (*out valid until the context's next call); a counter
+ * (include/lasp.hrl:60-63, 76): the orddict of its non-zero actors in term order */
 int laspj_var_etf_read(laspj_var* var, const uint8_t** out, uint64_t* out_len, int32_t* verdict);
-/* Type:value(#dv.value) — lasp_orset.erl:67-73 / lasp_gset.erl:74-76 */
+/* Type:value(#dv.value) — lasp_orset.erl:67-73 / lasp_gset.erl:74-76; a counter
+ * (lasp_lattice.erl:87-90 reads riak_dt_gcounter:value/1): term_to_binary(Sum) */
 int laspj_var_etf_value(laspj_var* var, const uint8_t** out, uint64_t* out_len,
                         int32_t* verdict);
 /* threshold_met(Type, #dv.value, Threshold) — lasp_lattice.erl:62-75, as read/6 asks it
  * (lasp_core.erl:331-364): is_inflation (strict = 0, Threshold) or is_strict_inflation
- * (strict = 1, {strict, Threshold}) of Threshold -> the variable's value */
+ * (strict = 1, {strict, Threshold}) of Threshold -> the variable's value; a counter
+ * (lasp_lattice.erl:87-90): `Threshold =< value(V)` (strict: `<`) as
+ * laspj_gcounter_threshold_plan plans it */
 int laspj_var_etf_threshold(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict,
                             int32_t* result, int32_t* verdict);
 /* 1 when the value (#dv.value, include/lasp.hrl:60-63) is on the device, 0 when it is
@@ -967,7 +1015,8 @@ int laspj_var_resident(const laspj_var* var, int32_t* resident);
  * of one namespace (laspj_var_create_replica); verdict FALLBACK otherwise (G-Sets — the
  * body's `LValue ++ RValue` is a list value —, variables of different namespaces,
  * host-held values): the NIF reads l and r and runs the body on their images
- * (laspj_list_etf_union) as before.  out may be l or r. */
+ * (laspj_list_etf_union) as before.  out may be l or r.  A counter (lasp_core.erl:602-627
+ * takes sets only): FALLBACK. */
 int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
                     int32_t* verdict);
 /* lasp_core:update/4 (lasp_core.erl:283-287) on the variable: {ok, Value} =
@@ -991,12 +1040,26 @@ int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
  * raises), a term `==` to one the namespace holds under another image, a token of another
  * image length in a wide namespace, a host-held variable — the NIF runs the reference's
  * update on the read value and writes the result (an element's 65th token widens the
- * namespace instead). */
+ * namespace instead).  A counter (lasp_core.erl:283-287: riak_dt_gcounter:update/3 reads
+ * its Actor): FALLBACK; laspj_var_etf_increment takes the Actor. */
 #define LASPJ_UPDATE_OK          0
 #define LASPJ_UPDATE_NOT_PRESENT 1
 int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_t* result,
                          const uint8_t** err_elem, uint64_t* err_len, const uint8_t** minted,
                          uint32_t* nminted, int32_t* verdict);
+/* lasp_core:update/4 (lasp_core.erl:283-287) on a counter: riak_dt_gcounter:update(increment
+ * | {increment, N}, Actor, #dv.value) — row[slot(Actor)] += N — with op and actor the
+ * term_to_binary/1 images of Op and Actor.  verdict FALLBACK (nothing changed, no actor
+ * registered): any other Op, N =< 0 or >= 2^64, a count that would pass 2^64 - 1, an Actor
+ * the namespace cannot take, a host-held value.  ids != NULL: the same kernel re-checks the
+ * variable's waiters against the new sum and the call answers ids / *nmet / *nwaiting
+ * exactly as laspj_var_recheck would have (write/4's reply_to_all, lasp_core.erl:765-825,
+ * 839-844): the advertisement counter's inner loop in one launch.  ids == NULL (cap 0; nmet
+ * and nwaiting may be NULL): the call returns once its kernel is enqueued.  A set variable:
+ * LASPJ_E_KIND. */
+int laspj_var_etf_increment(laspj_var* var, const uint8_t* op, uint64_t nop,
+                            const uint8_t* actor, uint64_t nactor, uint64_t* ids, uint32_t cap,
+                            uint32_t* nmet, uint32_t* nwaiting, int32_t* verdict);
 
 /* Blocking reads kept beside the variable: `#dv.waiting_threads` (include/lasp.hrl:60-63)
  * on the device.  A waiter is {id, strict, Threshold}; its threshold is decoded once, when
@@ -1014,7 +1077,10 @@ int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_
  * and nothing is kept; otherwise *met = 0 and the waiter is appended to the variable's
  * waiting_threads (strict = 1: {strict, Threshold}; the caller has replaced `undefined`
  * by Type:new(), whose image is []).  verdict FALLBACK (a host-held value, a threshold the
- * namespace cannot represent): nothing is registered. */
+ * namespace cannot represent): nothing is registered.  A counter's waiter
+ * (lasp_core.erl:331-364 over lasp_lattice.erl:87-90) is {id, strict, image, planned t}; one
+ * that can never be met (a non-number, t >= 2^64) is kept in list order and never fires,
+ * as the reference would queue it forever. */
 int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict,
                    uint64_t id, int32_t* met, int32_t* verdict);
 /* write/4's reply_to_all (lasp_core.erl:839-844, 765-825): every waiter of the variable
@@ -1031,7 +1097,8 @@ int laspj_var_recheck(laspj_var* var, uint64_t* ids, uint32_t cap, uint32_t* nme
 /* the same after laspj_var_etf_bind_many / a vnode's queued writes (lasp_vnode.erl:213-237;
  * lasp_core.erl:765-825 per variable): all waiters of n distinct variables of one context
  * in one device pass; ids grouped by variable in argument order, nmet[i] and verdict[i]
- * per variable.  More than cap met over all of them: nothing is removed. */
+ * per variable.  More than cap met over all of them: nothing is removed.  Counters and
+ * sets may be named together (lasp_vnode.erl:213-237 queues writes of any type). */
 int laspj_var_recheck_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars, uint64_t* ids,
                            uint32_t cap, uint32_t* nmet, int32_t* verdict);
 /* a waiter leaves before it was met (its process died: the first waiter with that id of

@@ -44,6 +44,7 @@ TUNE_NIF_PASSES = 14
 TUNE_LIST_CHUNK = 15
 NIF_OK, NIF_FALLBACK = 0, 1           # verdicts of the NIF-level entry points
 NIF_STATS = 20
+GC_NEVER, GC_ALWAYS, GC_T = 0, 1, 2
 
 
 class LaspjUnavailable(RuntimeError):
@@ -212,6 +213,10 @@ SIGNATURES = {
     "laspj_dict_info": (i, [vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64)]),
     "laspj_dict_export": (i, [vp, u32, vp, vp, vp, vp, vp, vp]),
     "laspj_dict_encode": (i, [vp, C.c_int32, vp, vp, u64, i, u32, vp, vp]),
+    "laspj_gcounter_etf_parse": (i, [vp, vp, u64, vp, vp, u32, C.POINTER(u32),
+                                     C.POINTER(C.c_int32)]),
+    "laspj_gcounter_etf_encode": (i, [vp, vp, vp, u32, vp, u64, C.POINTER(u64)]),
+    "laspj_gcounter_threshold_plan": (i, [vp, u64, i, C.POINTER(C.c_int32), C.POINTER(u64)]),
     "laspj_orset_etf_merge": (i, [vp, vp, u64, vp, u64, vpp, C.POINTER(u64),
                                   C.POINTER(C.c_int32)]),
     "laspj_orset_etf_merge_many": (i, [vp, u32, vp, vp, vp, vp, vp, vp, vp]),
@@ -242,6 +247,8 @@ SIGNATURES = {
     "laspj_var_union": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,
                                  C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_var_etf_increment": (i, [vp, vp, u64, vp, u64, vp, u32, C.POINTER(u32),
+                                    C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_var_wait": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_var_recheck": (i, [vp, vp, u32, C.POINTER(u32), C.POINTER(u32),
                               C.POINTER(C.c_int32)]),

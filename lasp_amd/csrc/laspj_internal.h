@@ -548,4 +548,71 @@ int list_ranks(const laspj_dict* dict, std::vector<uint32_t>* krank, std::vector
 int list_write(const laspj_dict* dict, int32_t kind, const ListItems& it, std::string* out);
 void list_etf_destroy(laspj_ctx* ctx);     // laspj_list_etf.cpp; call without ctx->mu held
 
+// ---- riak_dt_gcounter variables (laspj_counter_host.cpp, laspj_counters.hip) -----------
+// A counter variable is one row of uint64 counts over the actor slots of its namespace (a
+// host dictionary of element terms only, append-only); 0 = the actor is absent.
+constexpr uint32_t kGcMaxActors = 1u << 20;      // a namespace holds at most this many
+// one {Actor, Count} of an image as the kernels take it (16 bytes: one vector load)
+struct GcPair {
+    uint64_t count;
+    uint32_t slot;
+    uint32_t pad;
+};
+// the image [{Actor, Count}] (131 + the orddict) walked into pairs in list order, its
+// unseen actors registered; a LASPJ_DEC_* status (not OK: every registration of the call
+// undone through the dictionary's journal, no pairs) or LASPJ_E_NOMEM
+int gc_parse(laspj_dict* dict, const uint8_t* p, size_t n, std::vector<GcPair>* out);
+// pairs in term order -> 131 + the orddict as term_to_binary/1 writes it (zero counts skipped)
+void gc_encode(const laspj_dict* dict, const GcPair* pairs, size_t n, std::string* out);
+// a non-negative integer as term_to_binary/1 encodes it (97 / 98 / 110)
+void gc_put_uint(std::string* o, uint64_t v);
+// threshold_met(riak_dt_gcounter, V, T) (lasp_lattice.erl:87-90) planned from T's image:
+// LASPJ_GC_NEVER / LASPJ_GC_ALWAYS / LASPJ_GC_T with *t (`*t =< value(V)`), -1: not a term
+int gc_threshold_plan(const uint8_t* p, size_t n, bool strict, uint64_t* t);
+
+struct GcVar;                                    // laspj_counters.hip
+struct GcState;                                  // a context's counter variables and staging
+// what the counter path shares with the set path's state (laspj_nif.hip): the context's
+// call lock, its laspj_nif_stats counters and the slot its GcState hangs from
+struct GcHooks {
+    std::mutex* mu = nullptr;
+    uint64_t* stats = nullptr;
+    GcState** slot = nullptr;
+};
+bool nif_gc_hooks(laspj_ctx* ctx, GcHooks* h);
+// the entry points of include/laspj.h on a counter variable (each takes the call lock)
+int gc_var_create(laspj_ctx* ctx, GcVar* peer, GcVar** out);
+laspj_ctx* gc_var_ctx(const GcVar* v);
+int gc_var_destroy(GcVar* v);
+int gc_bind_many(laspj_ctx* ctx, uint32_t n, GcVar* const* vars, const uint8_t* const* values,
+                 const uint64_t* lens, int32_t* status, int32_t* verdict);
+int gc_write(GcVar* v, const uint8_t* value, uint64_t n, int32_t* verdict);
+int gc_read(GcVar* v, bool value, const uint8_t** out, uint64_t* out_len, int32_t* verdict);
+int gc_threshold(GcVar* v, const uint8_t* threshold, uint64_t n, int strict, int32_t* result,
+                 int32_t* verdict);
+int gc_resident(const GcVar* v, int32_t* resident);
+int gc_refuse(GcVar* v, int32_t* verdict);       // update / union: FALLBACK, counted
+int gc_wait(GcVar* v, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+            int32_t* met, int32_t* verdict);
+int gc_recheck(GcVar* v, uint64_t* ids, uint32_t cap, uint32_t* nmet, uint32_t* nwaiting,
+               int32_t* verdict);
+// recheck_many's two halves, call lock held by the caller (counters and sets together):
+// every waiter of the n counters checked (one device pass at most), nmet[i] / verdict[i]
+// answered and nothing removed; then the met ones' ids written in argument order and removed
+int gc_recheck_check(laspj_ctx* ctx, uint32_t n, GcVar* const* vars, uint32_t* nmet,
+                     int32_t* verdict);
+void gc_recheck_take(GcVar* v, uint64_t* ids);
+int gc_wait_cancel(GcVar* v, uint64_t id, int32_t* found);
+int gc_waiter_count(const GcVar* v, uint32_t* n);
+int gc_waiter_at(GcVar* v, uint32_t k, uint64_t* id, int32_t* strict, const uint8_t** threshold,
+                 uint64_t* n);
+int gc_increment(GcVar* v, const uint8_t* op, uint64_t nop, const uint8_t* actor, uint64_t nactor,
+                 uint64_t* ids, uint32_t cap, uint32_t* nmet, uint32_t* nwaiting,
+                 int32_t* verdict);
+uint64_t gc_dict_elements(const GcState* G);     // laspj_nif_stats [7]'s share
+// laspj_nif_reset (call lock held): rows written out to images, namespaces started afresh
+int gc_ctx_reset(laspj_ctx* ctx, GcState* G);
+// the context goes (call lock held, ctx->mu not): rows released, variables orphaned
+void gc_ctx_destroy(laspj_ctx* ctx, GcState* G);
+
 }  // namespace laspj

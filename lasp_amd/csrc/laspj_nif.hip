@@ -114,6 +114,9 @@ struct laspj_var {
     bool held = false;               // `image` is a value write/4 could not represent
     std::vector<uint8_t> image;      // host-held value (term_to_binary image)
     std::vector<laspj::Waiter> waiters;   // `#dv.waiting_threads`, in list order
+    // LASPJ_KIND_GCOUNTER: the variable lives in laspj_counters.hip and nothing above is
+    // used (ctx stays null, so a set path reached by mistake answers LASPJ_E_INVAL)
+    laspj::GcVar* gc = nullptr;
 };
 
 namespace laspj {
@@ -210,6 +213,7 @@ struct NifState {
     // minted, the image of the element a failed precondition names
     std::vector<uint8_t> minted;
     std::string err_elem;
+    GcState* gc = nullptr;          // the counter variables' state (laspj_counters.hip)
 };
 
 namespace {
@@ -2053,6 +2057,19 @@ NifState* state(laspj_ctx* ctx) {
     return ctx->nif;
 }
 
+}  // namespace
+
+bool nif_gc_hooks(laspj_ctx* ctx, GcHooks* h) {
+    NifState* S = state(ctx);
+    if (!S) return false;
+    h->mu = &S->mu;
+    h->stats = S->stats;
+    h->slot = &S->gc;
+    return true;
+}
+
+namespace {
+
 // A variable whose value sits in its host image (written out by a dictionary reset) gets
 // cells again: write/4 of that image.  *ok: the variable is resident over the current
 // dictionary (false: it stays host-held; its calls answer FALLBACK)
@@ -2236,6 +2253,8 @@ void nif_destroy(laspj_ctx* ctx) {
             v->ns->vars.clear();
         }
         S->vars.clear();
+        gc_ctx_destroy(ctx, S->gc);
+        S->gc = nullptr;
     }
     for (KindState& K : S->ks) free_ns(K);
     hipSetDevice(ctx->device);
@@ -2602,13 +2621,40 @@ void serve_binds(laspj_ctx* ctx, NifState* S, std::vector<BindReq*>& batch) {
 }  // namespace
 }  // namespace laspj
 
+namespace {
+
+// a LASPJ_KIND_GCOUNTER variable: the handle only carries its counter (laspj_counters.hip)
+int counter_new(laspj_ctx* ctx, laspj::GcVar* peer, laspj_var** out) {
+    auto* v = new (std::nothrow) laspj_var;
+    if (!v) return fail(ctx, LASPJ_E_NOMEM, "var_create: host allocation");
+    v->kind = LASPJ_KIND_GCOUNTER;
+    v->resident = false;
+    if (int s = laspj::gc_var_create(ctx, peer, &v->gc)) {
+        delete v;
+        return s;
+    }
+    *out = v;
+    return LASPJ_OK;
+}
+
+// the kinds named in a list of variables: bit 0 sets, bit 1 counters
+int kinds_of(uint32_t n, laspj_var* const* vars) {
+    int k = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (vars[i]) k |= vars[i]->gc ? 2 : 1;
+    return k;
+}
+
+}  // namespace
+
 extern "C" {
 
 int laspj_var_create(laspj_ctx* ctx, int32_t kind, laspj_var** out) {
     if (!ctx || !out) return LASPJ_E_INVAL;
     *out = nullptr;
+    if (kind == LASPJ_KIND_GCOUNTER) return counter_new(ctx, nullptr, out);
     if (kind != LASPJ_KIND_ORSET && kind != LASPJ_KIND_GSET)
-        return fail(ctx, LASPJ_E_KIND, "var_create: OR-Set or G-Set variables");
+        return fail(ctx, LASPJ_E_KIND, "var_create: OR-Set, G-Set or G-Counter variables");
     laspj::NifState* S = laspj::state(ctx);
     if (!S) return fail(ctx, LASPJ_E_NOMEM, "nif: state allocation");
     std::lock_guard<std::mutex> lk(S->mu);
@@ -2616,6 +2662,11 @@ int laspj_var_create(laspj_ctx* ctx, int32_t kind, laspj_var** out) {
 }
 
 int laspj_var_create_replica(laspj_var* peer, laspj_var** out) {
+    if (peer && peer->gc) {
+        if (!out || !laspj::gc_var_ctx(peer->gc)) return LASPJ_E_INVAL;
+        *out = nullptr;
+        return counter_new(laspj::gc_var_ctx(peer->gc), peer->gc, out);
+    }
     laspj::NifState* S = var_state(peer);
     if (!S || !out) return LASPJ_E_INVAL;
     *out = nullptr;
@@ -2627,6 +2678,11 @@ int laspj_var_create_replica(laspj_var* peer, laspj_var** out) {
 
 int laspj_var_destroy(laspj_var* v) {
     if (!v) return LASPJ_E_INVAL;
+    if (v->gc) {
+        laspj::gc_var_destroy(v->gc);
+        delete v;
+        return LASPJ_OK;
+    }
     // its waiters go with it (a context gone first took their cells as it took the
     // variable's: only the host side is left)
     auto drop_waiters = [v](laspj::NifState* S) {
@@ -2675,6 +2731,13 @@ int laspj_var_etf_bind_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars,
     if (!n) return LASPJ_OK;
     if (!vars || !values || !lens || !status || !verdict)
         return fail(ctx, LASPJ_E_INVAL, "var_bind: null array");
+    if (const int k = kinds_of(n, vars); k & 2) {
+        // counters: their own pass (laspj_counters.hip); never mixed with sets
+        if (k & 1) return fail(ctx, LASPJ_E_KIND, "var_bind: variables of one kind per call");
+        std::vector<laspj::GcVar*> gs(n, nullptr);
+        for (uint32_t i = 0; i < n; ++i) gs[i] = vars[i] ? vars[i]->gc : nullptr;
+        return laspj::gc_bind_many(ctx, n, gs.data(), values, lens, status, verdict);
+    }
     laspj::NifState* S = laspj::state(ctx);
     if (!S) return fail(ctx, LASPJ_E_NOMEM, "nif: state allocation");
     std::lock_guard<std::mutex> lk(S->mu);
@@ -2683,6 +2746,14 @@ int laspj_var_etf_bind_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars,
 
 int laspj_var_etf_bind(laspj_var* var, const uint8_t* value, uint64_t n, int32_t* status,
                        int32_t* verdict) {
+    if (var && var->gc) {
+        // a counter bind takes the call lock directly (no group-commit queue)
+        laspj_ctx* gctx = laspj::gc_var_ctx(var->gc);
+        if (!gctx) return LASPJ_E_INVAL;
+        if ((!value && n) || !status || !verdict)
+            return fail(gctx, LASPJ_E_INVAL, "var_bind: null argument");
+        return laspj::gc_bind_many(gctx, 1, &var->gc, &value, &n, status, verdict);
+    }
     if (!var || !var->ctx) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
     if ((!value && n) || !status || !verdict) return fail(ctx, LASPJ_E_INVAL, "var_bind: null argument");
@@ -2911,11 +2982,71 @@ int recheck_locked(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_var* co
     return LASPJ_OK;
 }
 
+// recheck_many over counters (and sets beside them), S->mu held: the counters are checked
+// first and nothing removed; the sets then answer as ever with the room the counters leave
+// (more met than that: they remove nothing either); the ids are laid out in argument order
+int recheck_mixed(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_var* const* vars,
+                  uint64_t* ids, uint32_t cap, uint32_t* nmet, int32_t* verdict) {
+    std::vector<laspj_var*> sets;
+    std::vector<laspj::GcVar*> gcs;
+    std::vector<uint32_t> sat, gat;
+    std::unordered_set<laspj_var*> seen;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!vars[i] || !seen.insert(vars[i]).second)
+            return fail(ctx, LASPJ_E_INVAL, "var_recheck: variable %u null or named twice", i);
+        if (vars[i]->gc) {
+            gcs.push_back(vars[i]->gc);
+            gat.push_back(i);
+        } else {
+            if (vars[i]->ctx != ctx || !S->vars.count(vars[i]))
+                return fail(ctx, LASPJ_E_INVAL, "var_recheck: variable %u is not this context's", i);
+            sets.push_back(vars[i]);
+            sat.push_back(i);
+        }
+    }
+    std::vector<uint32_t> gmet(gcs.size(), 0), smet(sets.size(), 0);
+    std::vector<int32_t> gvd(gcs.size(), LASPJ_NIF_FALLBACK), svd(sets.size(), LASPJ_NIF_FALLBACK);
+    if (int s = laspj::gc_recheck_check(ctx, (uint32_t)gcs.size(), gcs.data(), gmet.data(), gvd.data()))
+        return s;
+    uint64_t gtotal = 0;
+    for (uint32_t m : gmet) gtotal += m;
+    const uint32_t room = gtotal <= cap ? cap - (uint32_t)gtotal : 0;
+    std::vector<uint64_t> sids(room);
+    uint64_t stotal = 0;
+    if (!sets.empty()) {
+        if (int s = recheck_locked(ctx, S, (uint32_t)sets.size(), sets.data(),
+                                   room ? sids.data() : nullptr, room, smet.data(), svd.data()))
+            return s;
+        for (uint32_t m : smet) stotal += m;
+    }
+    for (size_t k = 0; k < gcs.size(); ++k) {
+        nmet[gat[k]] = gmet[k];
+        verdict[gat[k]] = gvd[k];
+    }
+    for (size_t k = 0; k < sets.size(); ++k) {
+        nmet[sat[k]] = smet[k];
+        verdict[sat[k]] = svd[k];
+    }
+    if (gtotal > cap || stotal > room || (gtotal + stotal && !ids)) return LASPJ_OK;
+    uint64_t at = 0, sfrom = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (vars[i]->gc) {
+            if (nmet[i]) laspj::gc_recheck_take(vars[i]->gc, ids + at);
+        } else {
+            for (uint32_t k = 0; k < nmet[i]; ++k) ids[at + k] = sids[sfrom + k];
+            sfrom += nmet[i];
+        }
+        at += nmet[i];
+    }
+    return LASPJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_t* verdict) {
+    if (var && var->gc) return laspj::gc_write(var->gc, value, n, verdict);
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -2927,6 +3058,7 @@ int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_
 
 int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
                    int32_t* met, int32_t* verdict) {
+    if (var && var->gc) return laspj::gc_wait(var->gc, threshold, n, strict, id, met, verdict);
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -2989,6 +3121,7 @@ int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int str
 
 int laspj_var_recheck(laspj_var* var, uint64_t* ids, uint32_t cap, uint32_t* nmet,
                       uint32_t* nwaiting, int32_t* verdict) {
+    if (var && var->gc) return laspj::gc_recheck(var->gc, ids, cap, nmet, nwaiting, verdict);
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -3011,6 +3144,7 @@ int laspj_var_recheck_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars, u
     laspj::NifState* S = laspj::state(ctx);
     if (!S) return fail(ctx, LASPJ_E_NOMEM, "nif: state allocation");
     std::lock_guard<std::mutex> lk(S->mu);
+    if (kinds_of(n, vars) & 2) return recheck_mixed(ctx, S, n, vars, ids, cap, nmet, verdict);
     std::unordered_set<laspj_var*> seen;
     for (uint32_t i = 0; i < n; ++i) {
         if (!vars[i] || vars[i]->ctx != ctx || !S->vars.count(vars[i]))
@@ -3022,6 +3156,7 @@ int laspj_var_recheck_many(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars, u
 }
 
 int laspj_var_wait_cancel(laspj_var* var, uint64_t id, int32_t* found) {
+    if (var && var->gc) return laspj::gc_wait_cancel(var->gc, id, found);
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -3040,6 +3175,7 @@ int laspj_var_wait_cancel(laspj_var* var, uint64_t id, int32_t* found) {
 }
 
 int laspj_var_waiter_count(const laspj_var* var, uint32_t* n) {
+    if (var && var->gc) return laspj::gc_waiter_count(var->gc, n);
     laspj::NifState* S = var_state(const_cast<laspj_var*>(var));
     if (!S || !n) return LASPJ_E_INVAL;
     std::lock_guard<std::mutex> lk(S->mu);
@@ -3049,6 +3185,7 @@ int laspj_var_waiter_count(const laspj_var* var, uint32_t* n) {
 
 int laspj_var_waiter_at(laspj_var* var, uint32_t k, uint64_t* id, int32_t* strict,
                         const uint8_t** threshold, uint64_t* n) {
+    if (var && var->gc) return laspj::gc_waiter_at(var->gc, k, id, strict, threshold, n);
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -3065,16 +3202,19 @@ int laspj_var_waiter_at(laspj_var* var, uint32_t k, uint64_t* id, int32_t* stric
 }
 
 int laspj_var_etf_read(laspj_var* var, const uint8_t** out, uint64_t* out_len, int32_t* verdict) {
+    if (var && var->gc) return laspj::gc_read(var->gc, false, out, out_len, verdict);
     return var_image_call(var, false, out, out_len, verdict);
 }
 
 int laspj_var_etf_value(laspj_var* var, const uint8_t** out, uint64_t* out_len,
                         int32_t* verdict) {
+    if (var && var->gc) return laspj::gc_read(var->gc, true, out, out_len, verdict);
     return var_image_call(var, true, out, out_len, verdict);
 }
 
 int laspj_var_etf_threshold(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict,
                             int32_t* result, int32_t* verdict) {
+    if (var && var->gc) return laspj::gc_threshold(var->gc, threshold, n, strict, result, verdict);
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -3105,6 +3245,12 @@ int laspj_var_etf_threshold(laspj_var* var, const uint8_t* threshold, uint64_t n
 
 int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
                     int32_t* verdict) {
+    if (out && out->gc) {
+        // riak_dt_gcounter is no type lasp_core:union/7 takes: the NIF runs the reference's
+        if (!l || !r || !status) return LASPJ_E_INVAL;
+        *status = LASPJ_BIND_NOOP;
+        return laspj::gc_refuse(out->gc, verdict);
+    }
     laspj::NifState* S = var_state(out);
     if (!S || !l || !r) return LASPJ_E_INVAL;
     laspj_ctx* ctx = out->ctx;
@@ -3160,6 +3306,7 @@ int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
 }
 
 int laspj_var_resident(const laspj_var* var, int32_t* resident) {
+    if (var && var->gc) return laspj::gc_resident(var->gc, resident);
     if (!var || !resident) return LASPJ_E_INVAL;
     *resident = var->ctx && var->resident ? 1 : 0;
     return LASPJ_OK;
@@ -3168,6 +3315,16 @@ int laspj_var_resident(const laspj_var* var, int32_t* resident) {
 int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_t* result,
                          const uint8_t** err_elem, uint64_t* err_len, const uint8_t** minted,
                          uint32_t* nminted, int32_t* verdict) {
+    if (var && var->gc) {
+        // riak_dt_gcounter:update/3 needs the Actor: laspj_var_etf_increment
+        if (!op || !nop || !result) return LASPJ_E_INVAL;
+        *result = LASPJ_UPDATE_OK;
+        if (err_elem) *err_elem = nullptr;
+        if (err_len) *err_len = 0;
+        if (minted) *minted = nullptr;
+        if (nminted) *nminted = 0;
+        return laspj::gc_refuse(var->gc, verdict);
+    }
     laspj::NifState* S = var_state(var);
     if (!S) return LASPJ_E_INVAL;
     laspj_ctx* ctx = var->ctx;
@@ -3378,7 +3535,7 @@ int laspj_nif_stats(laspj_ctx* ctx, uint64_t* out, uint32_t n) {
         };
         for (const laspj::KindState& K : S->ks) add(&K);
         for (const laspj_var* v : S->vars) add(v->ns.get());
-        out[7] = tot;
+        out[7] = tot + laspj::gc_dict_elements(S->gc);
     }
     return LASPJ_OK;
 }
@@ -3396,7 +3553,19 @@ int laspj_nif_reset(laspj_ctx* ctx) {
         if (seen.insert(v->ns.get()).second) nss.push_back(v->ns);
     for (auto& ns : nss)
         if (int s = laspj::reset_dict(ctx, S, *ns)) return s;
-    return LASPJ_OK;
+    return laspj::gc_ctx_reset(ctx, S->gc);
+}
+
+int laspj_var_etf_increment(laspj_var* var, const uint8_t* op, uint64_t nop, const uint8_t* actor,
+                            uint64_t nactor, uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                            uint32_t* nwaiting, int32_t* verdict) {
+    if (!var) return LASPJ_E_INVAL;
+    if (!var->gc) {
+        // lasp_orset / lasp_gset have no increment: laspj_var_etf_update serves their update/3
+        if (!var->ctx) return LASPJ_E_INVAL;
+        return fail(var->ctx, LASPJ_E_KIND, "var_increment: a G-Counter variable");
+    }
+    return laspj::gc_increment(var->gc, op, nop, actor, nactor, ids, cap, nmet, nwaiting, verdict);
 }
 
 }  // extern "C"

@@ -252,7 +252,7 @@ class Context:
 
 
 class NifVar:
-    """laspj_var: one OR-Set / G-Set `#dv.value` resident on the device (laspj.h
+    """laspj_var: one OR-Set / G-Set / G-Counter `#dv.value` resident on the device (laspj.h
     "resident variables").  Every call returns (verdict, answer) like the NIF image calls;
     answer is None on NIF_FALLBACK."""
 
@@ -263,8 +263,11 @@ class NifVar:
             self.kind = peer.kind
             check(self.L.laspj_var_create_replica(peer.h, C.byref(self.h)), ctx.h)
             return
-        k = _lib.KIND_GSET if kind == "gset" else _lib.KIND_ORSET
-        check(self.L.laspj_var_create(ctx.h, k, C.byref(self.h)), ctx.h)
+        kinds = {"orset": _lib.KIND_ORSET, "gset": _lib.KIND_GSET,
+                 "gcounter": _lib.KIND_GCOUNTER}
+        if kind not in kinds:
+            raise ValueError(f"NifVar: unknown kind {kind!r} (one of {sorted(kinds)})")
+        check(self.L.laspj_var_create(ctx.h, kinds[kind], C.byref(self.h)), ctx.h)
 
     def replica(self) -> "NifVar":
         """laspj_var_create_replica: another replica in this variable's namespace."""
@@ -284,6 +287,30 @@ class NifVar:
         err = C.string_at(eimg, elen.value) if res.value == 1 else None
         raw = C.string_at(mint, 20 * n.value) if n.value else b""
         return 0, int(res.value), err, [raw[20 * k:20 * k + 20] for k in range(n.value)]
+
+    def increment(self, op_img: bytes, actor_img: bytes, cap=None):
+        """lasp_core:update/4 on a G-Counter (laspj_var_etf_increment): op_img / actor_img
+        are the images of `increment | {increment, N}` and of the Actor.  cap None: (verdict,)
+        once the kernel is enqueued; else the fused re-check, (verdict, [ids met], waiters
+        left) as recheck answers (asking laspj_var_recheck again when more than cap fired:
+        the increment itself is applied once)."""
+        op_img, actor_img = bytes(op_img), bytes(actor_img)
+        verd = C.c_int32()
+        if cap is None:
+            check(self.L.laspj_var_etf_increment(self.h, op_img, len(op_img), actor_img,
+                                                 len(actor_img), None, 0, None, None,
+                                                 C.byref(verd)), self.ctx.h)
+            return (int(verd.value),)
+        ids = (C.c_uint64 * max(cap, 1))()
+        nmet, left = C.c_uint32(), C.c_uint32()
+        check(self.L.laspj_var_etf_increment(self.h, op_img, len(op_img), actor_img,
+                                             len(actor_img), ids, cap, C.byref(nmet),
+                                             C.byref(left), C.byref(verd)), self.ctx.h)
+        if verd.value != 0:
+            return int(verd.value), None, int(left.value)
+        if nmet.value > cap:
+            return self.recheck(nmet.value)
+        return 0, [int(x) for x in ids[:nmet.value]], int(left.value)
 
     def union(self, left: "NifVar", right: "NifVar"):
         """laspj_var_union: lasp_core:union/7's body over resident left / right (one
