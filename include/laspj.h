@@ -1019,6 +1019,69 @@ int laspj_var_resident(const laspj_var* var, int32_t* resident);
  * takes sets only): FALLBACK. */
 int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
                     int32_t* verdict);
+/* Resident filter processes.  lasp_process:process/3 (lasp_process.erl:61-95) re-runs
+ * filter/6's body (lasp_core.erl:681-712) whenever its input changes; the fun is an Erlang
+ * fun only the NIF can call, and pure (its results for the elements already seen do not
+ * change), so the device keeps them beside the variable: two bitmaps over the namespace's
+ * element slots, `evaluated` (F has been called for the element) and `keep` (it answered
+ * true).  A re-run in steady state is then one small kernel and one status word over PCIe.
+ * The NIF's loop: run; while pending > 0: args -> F on each -> results -> run; after a
+ * WRITTEN answer laspj_var_recheck(out).  The bitmaps follow the namespace: growth extends
+ * them with zeros, widening changes nothing (they are per element, not per token), a
+ * dictionary reset (laspj_nif_reset, or the 2^20 element cap) clears both and drops an
+ * outstanding argument list, so F is asked again. */
+typedef struct laspj_filter laspj_filter;
+/* One lasp_process running filter/6 (lasp_core.erl:681-712) from in into out: both OR-Sets
+ * or both G-Sets (a counter or mixed kinds: LASPJ_E_KIND) of one context and one namespace
+ * (out made by laspj_var_create_replica, or out == in; two namespaces: LASPJ_E_UNSUPPORTED —
+ * the NIF keeps the image path, laspj_list_etf_filter, for that process); null arguments:
+ * LASPJ_E_INVAL.  Several filters may share one in.  Destroying a variable a live filter
+ * names kills the filter: its later calls answer LASPJ_E_INVAL (laspj_filter_destroy still
+ * frees it). */
+int laspj_filter_create(laspj_var* in, laspj_var* out, laspj_filter** f);
+/* the process ends (lasp_process.erl:61-95 terminates): its tables are released */
+int laspj_filter_destroy(laspj_filter* f);
+/* One re-run of filter/6's body plus bind/3 (lasp_core.erl:681-712, 291-312).  The entries of
+ * in's value are the element slots holding any token (tombstoned ones too: the body keeps
+ * them) or a set G-Set bit; *pending = how many of them F has not been asked about.
+ * *pending > 0: out is untouched, *status LASPJ_BIND_NOOP — go through laspj_filter_args /
+ * laspj_filter_results and run again.  *pending == 0: AccValue = in's cells masked by keep;
+ * *status LASPJ_BIND_NOOP when out's cells equal AccValue's (`Value0 =:= Value`, :294-296),
+ * else out := merge(out, AccValue) and LASPJ_BIND_WRITTEN (also when the merge leaves out as
+ * it was: the reference writes then too).  verdict FALLBACK: in or out is held on the host.
+ * One synchronisation; the waiters of out are not re-checked (laspj_var_recheck after
+ * WRITTEN, as after laspj_var_union). */
+int laspj_filter_run(laspj_filter* f, int32_t* status, uint32_t* pending, int32_t* verdict);
+/* laspj_filter_run of n distinct filters of one context in one device pass — a vnode's
+ * queued re-runs (lasp_vnode.erl:213-237) — with one synchronisation; status, pending and
+ * verdict answered per filter; OR-Set and G-Set filters may be mixed.  LASPJ_E_INVAL when two
+ * of them share an out (their binds would race) or one reads another's out. */
+int laspj_filter_run_many(laspj_ctx* ctx, uint32_t n, laspj_filter* const* fs,
+                          int32_t* status, uint32_t* pending, int32_t* verdict);
+/* The arguments filter/6's body would call Function on and the device has no result for
+ * (lasp_core.erl:687-703): term_to_binary/1 of their list, one per pending element slot, in
+ * term order (the order the fold meets them in a canonical value); a G-Set element that is
+ * a 2-tuple gives its first component (`{X, _} -> X`, :688-695).  *count may be 0 (the image
+ * of []).  *out is valid until the context's next call; the filter remembers the slots it
+ * listed.  verdict FALLBACK as laspj_filter_run. */
+int laspj_filter_args(laspj_filter* f, const uint8_t** out, uint64_t* out_len,
+                      uint32_t* count, int32_t* verdict);
+/* Function's results for laspj_filter_args' list, in its order (lasp_core.erl:697-702):
+ * term_to_binary/1 of their list.  The atom true sets the element's keep bit (`true ->
+ * Acc ++ [Element]; _ -> Acc`); every listed element becomes evaluated.  LASPJ_E_INVAL with
+ * nothing recorded: a length other than the list's, or no list outstanding; after a
+ * dictionary reset dropped the list: LASPJ_OK with nothing recorded (the next run reports
+ * the elements pending again).  A fun that raised never gets here: the process crashes, as
+ * the reference's does. */
+int laspj_filter_results(laspj_filter* f, const uint8_t* results, uint64_t n);
+/* lasp_core:intersection/7 (lasp_core.erl:546-589) re-run over resident G-Sets of one
+ * namespace: AccValue = [X || X <- l, lists:member(X, r)] (:569-576), the AND of the
+ * bitmaps, then bind/3 into out (:291-312) with laspj_filter_run's status rule.  out may be
+ * l or r.  verdict FALLBACK: OR-Sets (the body's `Cx ++ Cy` is a list value), variables of
+ * different namespaces, host-held values, a namespace that has registered a 2-tuple element
+ * (the body takes its OR-Set branch on those, :561-568), a counter. */
+int laspj_var_intersection(laspj_var* out, laspj_var* l, laspj_var* r,
+                           int32_t* status, int32_t* verdict);
 /* lasp_core:update/4 (lasp_core.erl:283-287) on the variable: {ok, Value} =
  * Type:update(Op, Actor, Value0) (lasp_orset.erl:99-117, 222-262; lasp_gset.erl:84-88)
  * applied to the resident cells, then bind/3 of Value, which a successful update always

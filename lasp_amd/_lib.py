@@ -245,6 +245,13 @@ SIGNATURES = {
     "laspj_var_resident": (i, [vp, C.POINTER(C.c_int32)]),
     "laspj_var_create_replica": (i, [vp, vpp]),
     "laspj_var_union": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_filter_create": (i, [vp, vp, vpp]),
+    "laspj_filter_destroy": (i, [vp]),
+    "laspj_filter_run": (i, [vp, C.POINTER(C.c_int32), C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_filter_run_many": (i, [vp, u32, vp, vp, vp, vp]),
+    "laspj_filter_args": (i, [vp, vpp, C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_filter_results": (i, [vp, vp, u64]),
+    "laspj_var_intersection": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,
                                  C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_increment": (i, [vp, vp, u64, vp, u64, vp, u32, C.POINTER(u32),

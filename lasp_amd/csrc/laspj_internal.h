@@ -615,4 +615,32 @@ int gc_ctx_reset(laspj_ctx* ctx, GcState* G);
 // the context goes (call lock held, ctx->mu not): rows released, variables orphaned
 void gc_ctx_destroy(laspj_ctx* ctx, GcState* G);
 
+// ---- lasp_process re-runs over resident variables (laspj_process.hip) --------------------
+// One process of a pass: filter/6 (lasp_core.erl:681-712) — in's cells masked by keep, the
+// slots in holds and evaluated does not counted pending — or the G-Set intersection/7
+// (:569-576: keep = r's bitmap, evaluated null: nothing is ever pending).  n: element slots
+// (OR-Sets, tw {p, r} pairs each) or bitmap words (kProcGset); the bitmaps hold a bit per
+// element slot; pmask (or null): n's worth of bitmap words the check pass fills with the
+// pending slots.  out may be in.
+constexpr uint32_t kProcNarrow = 0, kProcWide = 1, kProcGset = 2;
+struct ProcDesc {
+    const uint64_t* in;
+    uint64_t* out;
+    const uint64_t* keep;
+    const uint64_t* evaluated;
+    uint64_t* pmask;
+    uint32_t n, tw, mode;
+    uint32_t block0;                // its first block of a launch over many
+};
+static_assert(sizeof(ProcDesc) == 56, "descriptor layout");
+// kProcCheck: rec {pending, changed} (zeroed by the caller) and pmask written, no cell
+// touched; kProcWrite: out |= AccValue where rec says pending == 0 and changed;
+// kProcFused: changed decided and out written in one pass (evaluated null only)
+constexpr uint32_t kProcCheck = 0, kProcWrite = 1, kProcFused = 2;
+uint32_t proc_blocks(const ProcDesc& d);
+hipError_t launch_proc_one(laspj_ctx* ctx, const ProcDesc& d, uint32_t* rec, uint32_t pass);
+// descs: n descriptors on the device (block0 ascending), rec: 2 n words, blocks: their sum
+hipError_t launch_proc_many(laspj_ctx* ctx, const ProcDesc* descs, uint32_t n, uint32_t blocks,
+                            uint32_t* rec, uint32_t pass);
+
 }  // namespace laspj

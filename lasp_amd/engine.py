@@ -226,6 +226,22 @@ class Context:
             at += nmet[k]
         return out
 
+    def filter(self, in_var: "NifVar", out_var: "NifVar") -> "NifFilter":
+        """laspj_filter_create: a resident lasp_process running filter/6 from in_var into
+        out_var (one namespace), the fun's results kept on the device."""
+        return NifFilter(self, in_var, out_var)
+
+    def filter_run_many(self, filters):
+        """laspj_filter_run_many: one re-run of each filter in one device pass —
+        [(verdict, status, pending)] per filter."""
+        n = len(filters)
+        if n == 0:
+            return []
+        fs = (C.c_void_p * n)(*[f.h.value for f in filters])
+        st, pend, verd = (C.c_int32 * n)(), (C.c_uint32 * n)(), (C.c_int32 * n)()
+        check(self.L.laspj_filter_run_many(self.h, n, fs, st, pend, verd), self.h)
+        return [(int(verd[k]), int(st[k]), int(pend[k])) for k in range(n)]
+
     def nif_stats(self) -> dict:
         out = (C.c_uint64 * _lib.NIF_STATS)()
         check(self.L.laspj_nif_stats(self.h, out, _lib.NIF_STATS), self.h)
@@ -320,6 +336,14 @@ class NifVar:
               self.ctx.h)
         return int(verd.value), int(st.value)
 
+    def intersection(self, left: "NifVar", right: "NifVar"):
+        """laspj_var_intersection: lasp_core:intersection/7's body over resident G-Sets
+        left / right (one namespace) bound into this variable — (verdict, status)."""
+        st, verd = C.c_int32(), C.c_int32()
+        check(self.L.laspj_var_intersection(self.h, left.h, right.h, C.byref(st),
+                                            C.byref(verd)), self.ctx.h)
+        return int(verd.value), int(st.value)
+
     def close(self):
         if self.h:
             self.L.laspj_var_destroy(self.h)
@@ -406,6 +430,66 @@ class NifVar:
                                              C.byref(p), C.byref(ln)), self.ctx.h)
             out.append((int(wid.value), bool(strict.value), C.string_at(p, ln.value)))
         return out
+
+
+class NifFilter:
+    """laspj_filter: a resident lasp_process running filter/6 (laspj.h "resident filter
+    processes").  run / args answer (verdict, ...) like the variable calls."""
+
+    def __init__(self, ctx: Context, in_var: NifVar, out_var: NifVar):
+        self.ctx, self.L = ctx, ctx.L
+        self.in_var, self.out_var = in_var, out_var
+        self.h = C.c_void_p()
+        check(self.L.laspj_filter_create(in_var.h, out_var.h, C.byref(self.h)), ctx.h)
+
+    def run(self):
+        """laspj_filter_run: (verdict, status, pending) — pending > 0: out is untouched,
+        go through args / results and run again; else status 0 no-op, 1 written."""
+        st, pend, verd = C.c_int32(), C.c_uint32(), C.c_int32()
+        check(self.L.laspj_filter_run(self.h, C.byref(st), C.byref(pend), C.byref(verd)),
+              self.ctx.h)
+        return int(verd.value), int(st.value), int(pend.value)
+
+    def args(self):
+        """laspj_filter_args: (verdict, image of the pending arguments' list, count)."""
+        out, olen, cnt, verd = C.c_void_p(), C.c_uint64(), C.c_uint32(), C.c_int32()
+        check(self.L.laspj_filter_args(self.h, C.byref(out), C.byref(olen), C.byref(cnt),
+                                       C.byref(verd)), self.ctx.h)
+        if verd.value != 0:
+            return int(verd.value), None, 0
+        return 0, C.string_at(out, olen.value), int(cnt.value)
+
+    def results(self, image: bytes):
+        """laspj_filter_results: the fun's results for the last args list, as a list image."""
+        image = bytes(image)
+        check(self.L.laspj_filter_results(self.h, image, len(image)), self.ctx.h)
+
+    def step(self, fun, max_rounds: int = 8):
+        """The Erlang side's loop for one re-run (the stand-in for the NIF): run; while
+        elements are pending, args -> fun on each decoded argument -> results -> run.
+        (verdict, status, pending) of the last run."""
+        from . import etf
+        for _ in range(max_rounds):
+            verd, st, pend = self.run()
+            if verd != 0 or pend == 0:
+                return verd, st, pend
+            verd, img, _n = self.args()
+            if verd != 0:
+                return verd, 0, pend
+            res = [fun(a) for a in etf.binary_to_term(img)]
+            self.results(etf.term_to_binary(res))
+        raise RuntimeError("NifFilter.step: elements still pending")
+
+    def close(self):
+        if self.h:
+            self.L.laspj_filter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def device_count() -> int:
