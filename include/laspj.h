@@ -1175,6 +1175,73 @@ int laspj_var_waiter_count(const laspj_var* var, uint32_t* n);
 int laspj_var_waiter_at(laspj_var* var, uint32_t k, uint64_t* id, int32_t* strict,
                         const uint8_t** threshold, uint64_t* n);
 
+/* Lazy threads and one-pass reads: `#dv.lazy_threads` (include/lasp.hrl:60-63) beside the
+ * variable, and the read side's entry points that walk it.  A lazy entry is {id,
+ * Threshold}: its threshold is decoded once into cells of the variable's namespace, exactly
+ * as a waiter's is (widened, grown, written out and decoded again across a dictionary
+ * reset), its image kept on the host.  Each call below decodes its thresholds and checks
+ * them in ONE device pass (the check rides behind the decode, one synchronisation; a call
+ * naming OR-Sets and G-Sets takes one pass per kind; unknown terms register and take
+ * another, as everywhere).  write/4 builds a fresh #dv (lasp_core.erl:842-843): every call
+ * that answers LASPJ_BIND_WRITTEN or LASPJ_UPDATE_OK on a set variable (bind, bind_many,
+ * update, union, filter run / run_many, intersection) and laspj_var_etf_write empty its
+ * lazy list.  Counters keep none: a counter's lazy threshold is a number, which
+ * reply_to_all hands to riak_dt_gcounter:value/1 as a value (:798 over
+ * lasp_lattice.erl:87-90) and crashes there, so these calls answer FALLBACK for them and
+ * laspj_var_wait remains the counter's read.
+ *
+ * wait_needed/6 (lasp_core.erl:730-758): threshold_met(Type, Value, Threshold) answered as
+ * laspj_var_etf_threshold answers it.  Met -> *needed = 1, nothing kept; unmet with a
+ * non-empty waiting_threads (:739-741) -> *needed = 1, nothing kept; unmet otherwise -> the
+ * lazy entry {id, Threshold} is appended and *needed = 0.  strict = 1 that would register:
+ * the stored {strict, T} is later handed to is_inflation as a value (:798) and crashes
+ * there — verdict FALLBACK, nothing kept; so for a counter, a host-held value and a
+ * threshold the namespace cannot represent.  The bare-pid entry (`undefined`, :744-746)
+ * cannot be reached for set types (the threshold_met call ahead of it raises): not built. */
+int laspj_var_wait_needed(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict,
+                          uint64_t id, int32_t* needed, int32_t* verdict);
+/* read/6 (lasp_core.erl:331-364), lazy threads included (the caller has replaced
+ * `undefined` by [], as for laspj_var_wait).  First reply_to_all(LazyThreads, {ok,
+ * Threshold}) (:348-349, 795-813): lazy entry j fires when threshold_met(Type,
+ * LazyThreshold_j, Threshold) holds — is_inflation, or is_strict_inflation for a strict
+ * read, from the read's threshold to the lazy one; the fired ids go to lazy_ids[0 ..
+ * *nlazy) in list order.  More fired than cap: nothing is changed or registered, *nlazy >
+ * cap says how much room to come back with.  Then threshold_met(Type, Value, Threshold)
+ * (:352): met -> *met = 1 and the lazy list stays as it was (:353-354 reply but do not
+ * store StillLazy: the fired entries stay and fire again on the next read); unmet -> *met
+ * = 0, the waiter {id, strict, Threshold} is appended to waiting_threads (the waiter
+ * laspj_var_wait makes: laspj_var_recheck serves it) and the fired entries are removed
+ * (:362).  *nstill_lazy: the lazy list's length after the call.  verdict FALLBACK (a
+ * host-held value, a threshold the namespace cannot represent, a counter): nothing fires,
+ * nothing is kept.  Without lazy threads: laspj_var_wait's met, verdict and waiter. */
+int laspj_var_read(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                   int32_t* met, uint64_t* lazy_ids, uint32_t cap, uint32_t* nlazy,
+                   uint32_t* nstill_lazy, int32_t* verdict);
+/* read_any/3 (lasp_core.erl:371-420): the fold of :372-414 over n {variable, threshold}
+ * pairs of one context.  *found: the first read that is met, or -1.  Each read i <=
+ * *found (all when -1) walks its variable's lazy threads by laspj_var_read's rules (kept
+ * on a met read, removed on an unmet one); its fired ids go into lazy_ids grouped by read
+ * in argument order, nlazy[i] of them.  Each read i < *found (all when -1) appends its
+ * waiter {id, strict[i], threshold i}.  Reads after *found do nothing (nlazy[i] = 0).  A
+ * variable may be named again: a later read of it sees the waiter and the removals of the
+ * earlier one.  More fired in all than cap: nothing is changed.  One verdict for the
+ * call: FALLBACK, nothing changed, when any variable is a counter or host-held or any
+ * threshold is not representable; a variable of another context: LASPJ_E_INVAL. */
+int laspj_var_read_any(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars,
+                       const uint8_t* const* thresholds, const uint64_t* lens,
+                       const int32_t* strict, uint64_t id, int32_t* found, uint64_t* lazy_ids,
+                       uint32_t cap, uint32_t* nlazy, int32_t* verdict);
+/* length(`#dv.lazy_threads`) (include/lasp.hrl:60-63); 0 for a counter */
+int laspj_var_lazy_count(const laspj_var* var, uint32_t* n);
+/* the k-th lazy entry in list order (lasp_core.erl:795-813 walks them so): its id and its
+ * threshold image as registered (valid until the variable's next call); LASPJ_E_RANGE past
+ * the last.  The NIF's walk behind a FALLBACK verdict. */
+int laspj_var_lazy_at(laspj_var* var, uint32_t k, uint64_t* id, const uint8_t** threshold,
+                      uint64_t* n);
+/* a lazy entry leaves (its process died, or the NIF's own walk replied to it): the first
+ * with that id of `#dv.lazy_threads` (include/lasp.hrl:60-63); *found 0 when there is none */
+int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found);
+
 /* counters of this context's NIF path: [0] calls, [1] device passes, [2] dictionary
  * registrations, [3] dictionary resets, [4] device image rebuilds, [5] host-encoded passes
  * (token images of mixed lengths), [6] FALLBACK verdicts, [7] dictionary elements (both

@@ -264,6 +264,15 @@ SIGNATURES = {
     "laspj_var_waiter_count": (i, [vp, C.POINTER(u32)]),
     "laspj_var_waiter_at": (i, [vp, u32, C.POINTER(u64), C.POINTER(C.c_int32), vpp,
                                 C.POINTER(u64)]),
+    "laspj_var_wait_needed": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32)]),
+    "laspj_var_read": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32), vp, u32, C.POINTER(u32),
+                           C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_var_read_any": (i, [vp, u32, vp, vp, vp, vp, u64, C.POINTER(C.c_int32), vp, u32, vp,
+                               C.POINTER(C.c_int32)]),
+    "laspj_var_lazy_count": (i, [vp, C.POINTER(u32)]),
+    "laspj_var_lazy_at": (i, [vp, u32, C.POINTER(u64), vpp, C.POINTER(u64)]),
+    "laspj_var_lazy_cancel": (i, [vp, u64, C.POINTER(C.c_int32)]),
     "laspj_list_etf_args": (i, [vp, C.c_int32, vp, u64, vpp, C.POINTER(u64),
                                 C.POINTER(C.c_int32)]),
     "laspj_list_etf_map": (i, [vp, C.c_int32, vp, u64, vp, u64, vpp, C.POINTER(u64),

@@ -643,4 +643,58 @@ hipError_t launch_proc_one(laspj_ctx* ctx, const ProcDesc& d, uint32_t* rec, uin
 hipError_t launch_proc_many(laspj_ctx* ctx, const ProcDesc* descs, uint32_t n, uint32_t blocks,
                             uint32_t* rec, uint32_t pass);
 
+// ---- the read side's check over resident variables (laspj_reads.hip) ---------------------
+// read/6, read_any/3 and wait_needed/6 (lasp_core.erl:331-420, 730-758): one previous state
+// per read (its threshold's cells) against its currents — the variable's value first, then
+// the variable's lazy thresholds in list order.  A read's wave items are the tiles of
+// kReadTile 16-byte units covering the longest of its blocks of cells.
+constexpr uint32_t kReadTile = 128;     // units per wave item: two per lane
+constexpr uint32_t kReadChunk = 16;     // currents per descriptor hand-round
+constexpr uint32_t kReadNarrow = 0, kReadWide = 1, kReadGset = 2;
+struct ReadDesc {
+    const uint64_t* cells;              // the threshold's cells (null: [])
+    uint32_t words;                     // u64 words of `cells`
+    uint32_t mode_strict;               // mode << 1 | strict
+    uint32_t c0, nc;                    // its currents: ReadCur [c0, c0 + nc)
+    uint64_t item0;                     // its first wave item
+};
+struct ReadCur {
+    const uint64_t* cells;
+    uint32_t words;
+    uint32_t read;                      // the read it belongs to
+};
+static_assert(sizeof(ReadDesc) == 32 && sizeof(ReadCur) == 16, "descriptor layout");
+// the records of n reads over ncs currents: {flags, n_current} x ncs, then n_previous x n
+inline uint64_t read_rec_bytes(uint32_t n, uint32_t ncs) { return 8ull * ncs + 4ull * n; }
+// rds / cs as the device reads them, rec: read_rec_bytes of device memory (zeroed here),
+// met: ncs bytes (current j of read i met: threshold_met(Type, C_j, T_i)); two launches on
+// the context's stream, no synchronisation
+hipError_t launch_read_check(laspj_ctx* ctx, const ReadDesc* rds, uint32_t n, const ReadCur* cs,
+                             uint32_t ncs, uint64_t items, uint32_t* rec, uint8_t* met);
+
+// the host's half (laspj_reads_host.cpp: no device, no lock)
+// wave items of a read whose longest block of cells has `words` u64 words
+inline uint64_t read_tiles(uint64_t words) {
+    return ((words + 1) / 2 + kReadTile - 1) / kReadTile;
+}
+// item0 of n descriptors from their tiles (tiles[i] from read_tiles); the total
+uint64_t read_lay_items(ReadDesc* rds, uint32_t n, const uint64_t* tiles);
+// The fold of read_any/3 (lasp_core.erl:372-414) over the device's answers.  Read i names
+// variable var_of[i] (dense, < nvars; a variable may be named again), whose lazy list had
+// nlazy[var] entries when the call began; ans[i]: 1 + nlazy[var] met bytes, the value's then
+// one per lazy entry.  A read is visited while none before it was met: its fired entries
+// are those still in the list (reply_to_all, :795-813); met ends the fold and stores
+// nothing (:353-354, 399-400); unmet blocks — a waiter, and the fired entries leave (:362,
+// :408).
+struct ReadFold {
+    int32_t found = -1;                          // the first met read, or -1
+    std::vector<std::vector<uint32_t>> fired;    // per read: positions in its variable's
+                                                 // list as the call found it, in list order
+    std::vector<uint8_t> blocked;                // per read: it leaves a waiter
+    std::vector<std::vector<uint32_t>> still;    // per variable: the positions that stay
+    uint64_t total = 0;                          // fired ids over all reads
+};
+void read_fold(uint32_t n, const uint32_t* var_of, uint32_t nvars, const uint32_t* nlazy,
+               const uint8_t* const* ans, ReadFold* out);
+
 }  // namespace laspj

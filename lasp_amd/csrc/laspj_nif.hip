@@ -48,6 +48,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <new>
 #include <unordered_set>
@@ -101,6 +102,16 @@ struct Waiter {
     laspj_var* cells = nullptr;
 };
 
+// One entry of `#dv.lazy_threads` ({threshold, wait, From, Type, Threshold},
+// lasp_core.erl:730-758), kept as a Waiter's threshold is: decoded once into a hidden
+// variable of the namespace.  (The bare-pid entry of :744-746 cannot be reached for the set
+// types: threshold_met(Type, Value, undefined) ahead of it raises.)
+struct Lazy {
+    uint64_t id = 0;
+    std::vector<uint8_t> image;
+    laspj_var* cells = nullptr;
+};
+
 }  // namespace laspj
 
 // A device-resident variable's value (the `#dv.value` of lasp_core's store): cells over its
@@ -119,6 +130,7 @@ struct laspj_var {
     bool held = false;               // `image` is a value write/4 could not represent
     std::vector<uint8_t> image;      // host-held value (term_to_binary image)
     std::vector<laspj::Waiter> waiters;   // `#dv.waiting_threads`, in list order
+    std::vector<laspj::Lazy> lazy;        // `#dv.lazy_threads`, in list order
     // LASPJ_KIND_GCOUNTER: the variable lives in laspj_counters.hip and nothing above is
     // used (ctx stays null, so a set path reached by mistake answers LASPJ_E_INVAL)
     laspj::GcVar* gc = nullptr;
@@ -230,6 +242,14 @@ struct NifState {
     uint8_t* hout_d = nullptr;
     const void* hin_dkey = nullptr;
     const void* hout_dkey = nullptr;
+    // the read check's own blocks (read_pass: its launches ride behind a pass that is using
+    // the four above): pinned [ReadDesc | ReadCur | met bytes] and the device records
+    void* rd_h = nullptr;
+    uint64_t rd_h_bytes = 0;
+    uint8_t* rd_hd = nullptr;
+    const void* rd_hkey = nullptr;
+    void* rd_d = nullptr;
+    uint64_t rd_d_bytes = 0;
     uint64_t ocap = 1 << 20;        // bytes reserved for answer payloads
     // the operand cells known to be zero (the fused merge and the variable kernel clear
     // them behind them), so the next call's decoders need no memset
@@ -677,6 +697,10 @@ struct Call {
     // a merge whose decoders took new tokens: its operands' cells stay on the device and
     // the next pass only joins and writes (the images patched with the tokens first)
     bool write_only = false;
+    // launches that ride behind the answer's, ahead of the pass's one synchronisation (every
+    // pass of the call runs it again; ctx->mu is held): the read check behind its
+    // thresholds' decode (read_pass)
+    std::function<int()> tail;
 };
 
 // the group payload i belongs to
@@ -1624,7 +1648,9 @@ int collect_answers(NifState* S, Call& c, const PassPlan& P, const PassLayout& L
 //
 // What the phases must keep as it is:
 //   - for any call the same HIP operations reach ctx->stream in the same order (memsets,
-//     pulls, gathers, copies, kernels), and a pass synchronises exactly once;
+//     pulls, gathers, copies, kernels), and a pass synchronises exactly once (a call's
+//     `tail`, which only the read side sets, adds its launches last, ahead of that
+//     synchronisation);
 //   - ctx->mu (Guard) is held over fit_pass, over the waiters' payloads' gather inside
 //     stage_operands, and from pull_operands to the end — not over the rest of
 //     stage_operands (the offsets, the segment tables' copy into pinned memory, the host
@@ -1649,6 +1675,8 @@ int device_pass(laspj_ctx* ctx, NifState* S, Call& c) {
     if (int s = pull_operands(ctx, c, P, L, M, &t_copy)) return s;
     if (int s = enqueue_decode(ctx, S, c, P, L, M, hst, &cjob)) return s;
     if (int s = enqueue_answer(ctx, S, c, P, L, M, &cjob)) return s;
+    if (c.tail)
+        if (int s = c.tail()) return s;
     const uint64_t t1 = now_ns();
     LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t t2 = now_ns();
@@ -2303,6 +2331,8 @@ void nif_destroy(laspj_ctx* ctx) {
     if (S->dcells) hipFree(S->dcells);
     if (S->hin) hipHostFree(S->hin);
     if (S->hout) hipHostFree(S->hout);
+    if (S->rd_d) hipFree(S->rd_d);
+    if (S->rd_h) hipHostFree(S->rd_h);
     for (const PinSlot& p : S->pins) hipHostFree(p.h);
     delete S;
     ctx->nif = nullptr;
@@ -2538,6 +2568,28 @@ int var_new(laspj_ctx* ctx, laspj::NifState* S, int32_t kind,
     return LASPJ_OK;
 }
 
+// write/4 builds a fresh #dv (lasp_core.erl:842-843): the variable's lazy threads go, their
+// hidden cells with them (S->mu held; locked: ctx->mu is held too)
+void lazy_clear(laspj::NifState* S, laspj_var* v, bool locked = false) {
+    if (v->lazy.empty()) return;
+    for (laspj::Lazy& z : v->lazy) {
+        laspj_var* c = z.cells;
+        if (c && c->ctx) {
+            S->vars.erase(c);
+            c->ns->vars.erase(c);
+            if (locked) {
+                laspj::release_cells(c->ctx, c);
+            } else {
+                std::lock_guard<std::mutex> lk(c->ctx->mu);
+                hipSetDevice(c->ctx->device);
+                laspj::release_cells(c->ctx, c);
+            }
+        }
+        delete c;
+    }
+    v->lazy.clear();
+}
+
 // the tokens unique/1 mints (lasp_orset.erl:261-262: crypto:strong_rand_bytes(20)), from the
 // kernel's CSPRNG
 bool strong_rand(uint8_t* p, size_t n) {
@@ -2607,6 +2659,7 @@ int bind_many_locked(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_var* 
     for (size_t k = 0; k < live.size(); ++k) {
         verdict[live[k]] = vd[k];
         status[live[k]] = vd[k] == LASPJ_NIF_OK ? (int32_t)c.res[k] : 0;
+        if (status[live[k]] == LASPJ_BIND_WRITTEN) lazy_clear(S, vars[live[k]]);
     }
     return LASPJ_OK;
 }
@@ -2723,20 +2776,23 @@ int laspj_var_destroy(laspj_var* v) {
         delete v;
         return LASPJ_OK;
     }
-    // its waiters go with it (a context gone first took their cells as it took the
-    // variable's: only the host side is left)
+    // its waiters and lazy threads go with it (a context gone first took their cells as it
+    // took the variable's: only the host side is left)
     auto drop_waiters = [v](laspj::NifState* S) {
-        for (laspj::Waiter& w : v->waiters) {
-            if (w.cells && w.cells->ctx && S) {
-                S->vars.erase(w.cells);
-                w.cells->ns->vars.erase(w.cells);
-                std::lock_guard<std::mutex> lk2(w.cells->ctx->mu);
-                hipSetDevice(w.cells->ctx->device);
-                laspj::release_cells(w.cells->ctx, w.cells);
+        auto drop = [S](laspj_var* c) {
+            if (c && c->ctx && S) {
+                S->vars.erase(c);
+                c->ns->vars.erase(c);
+                std::lock_guard<std::mutex> lk2(c->ctx->mu);
+                hipSetDevice(c->ctx->device);
+                laspj::release_cells(c->ctx, c);
             }
-            delete w.cells;
-        }
+            delete c;
+        };
+        for (laspj::Waiter& w : v->waiters) drop(w.cells);
+        for (laspj::Lazy& z : v->lazy) drop(z.cells);
         v->waiters.clear();
+        v->lazy.clear();
     };
     if (v->ctx) {
         laspj::NifState* S = laspj::state(v->ctx);
@@ -3089,6 +3145,282 @@ int recheck_mixed(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_var* con
     return LASPJ_OK;
 }
 
+// one read of a read pass: a threshold image against the variable's value and — walk:
+// reply_to_all's (lasp_core.erl:795-813) — against its lazy thresholds
+struct ReadReq {
+    laspj_var* var;
+    const uint8_t* p;
+    uint64_t len;
+    int strict;
+    bool walk;
+};
+
+// The device's half of read/6, read_any/3 and wait_needed/6 (lasp_core.erl:331-420,
+// 730-758) over n reads of set variables of this context, S->mu held.  All n thresholds are
+// decoded into fresh hidden variables of their variables' namespaces by the multi-operand
+// write path (Op::WRITE, grouped by namespace as bind_many groups its payloads; unknown
+// terms register and decode again as there; one run per kind named, since a pass decodes
+// one kind), and k_read_check rides on the last run's passes behind the decode: one
+// synchronisation when every term is known and the reads are of one kind.  verdict OK:
+// hidden[i] holds threshold i's cells (the caller keeps it as a waiter's or a lazy entry's,
+// or drops it) and ans[i] the met bytes of read i — the value's, then one per lazy entry
+// when it walks.  verdict FALLBACK (a host-held value or lazy threshold, a threshold the
+// namespace cannot represent): no hidden variable is left.
+int read_pass(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, const ReadReq* rq,
+              std::vector<laspj_var*>* hidden, std::vector<std::vector<uint8_t>>* ans,
+              int32_t* verdict) {
+    using laspj::KindState;
+    *verdict = LASPJ_NIF_FALLBACK;
+    hidden->assign(n, nullptr);
+    ans->assign(n, {});
+    auto drop_all = [&] {
+        for (laspj_var*& h : *hidden) {
+            waiter_cells_drop(S, h);
+            h = nullptr;
+        }
+    };
+    auto fallback = [&] {
+        drop_all();
+        ++S->stats[laspj::ST_FALLBACKS];
+        return LASPJ_OK;
+    };
+    auto current = [](const laspj_var* v) { return v->resident && v->epoch == v->ns->epoch; };
+    // every block of cells the check reads is of its namespace's current dictionary
+    auto all_current = [&] {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!current(rq[i].var)) return false;
+            if ((*hidden)[i] && !current((*hidden)[i])) return false;
+            if (rq[i].walk)
+                for (const laspj::Lazy& z : rq[i].var->lazy)
+                    if (!current(z.cells)) return false;
+        }
+        return true;
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        bool ok = false;
+        if (int s = laspj::hydrate(ctx, S, rq[i].var, &ok)) return s;
+        for (size_t k = 0; ok && rq[i].walk && k < rq[i].var->lazy.size(); ++k)
+            if (int s = laspj::hydrate(ctx, S, rq[i].var->lazy[k].cells, &ok)) return s;
+        if (!ok) return fallback();
+    }
+    // (a decode above may have started a namespace's dictionary afresh and written the
+    // cells decoded before it out again: FALLBACK this once, as recheck_pass answers)
+    if (!all_current()) return fallback();
+    uint32_t ncs = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int s = var_new(ctx, S, rq[i].var->kind, rq[i].var->ns, &(*hidden)[i])) {
+            drop_all();
+            return s;
+        }
+        ncs += 1 + (rq[i].walk ? (uint32_t)rq[i].var->lazy.size() : 0);
+    }
+    // pinned: [ReadDesc x n | ReadCur x ncs | met x ncs]; device: the records
+    const uint64_t o_cs = 32ull * n, o_met = o_cs + 16ull * ncs, h_bytes = o_met + ncs;
+    {
+        laspj::Guard g(ctx);
+        int s = laspj::grow_host(ctx, &S->rd_h, &S->rd_h_bytes, h_bytes);
+        if (!s) s = laspj::grow_dev(ctx, &S->rd_d, &S->rd_d_bytes, laspj::read_rec_bytes(n, ncs));
+        if (!s && S->rd_hkey != S->rd_h) {
+            void* hd = nullptr;
+            if (hipHostGetDevicePointer(&hd, S->rd_h, 0) != hipSuccess) {
+                hipGetLastError();
+                s = fail(ctx, LASPJ_E_DEVICE, "var_read: pinned block's device address");
+            } else {
+                S->rd_hd = static_cast<uint8_t*>(hd);
+                S->rd_hkey = S->rd_h;
+            }
+        }
+        if (s) {
+            drop_all();
+            return s;
+        }
+    }
+    bool launched = false;          // the last pass enqueued the check
+    std::vector<uint64_t> tiles(n);
+    // behind a pass's write kernel, ctx->mu held (the hidden cells are fitted by the pass)
+    auto tail = [&]() -> int {
+        launched = false;
+        if (!all_current()) return LASPJ_OK;      // (a reset inside the call: FALLBACK below)
+        auto* hd = reinterpret_cast<laspj::ReadDesc*>(S->rd_h);
+        auto* hc = reinterpret_cast<laspj::ReadCur*>(static_cast<uint8_t*>(S->rd_h) + o_cs);
+        auto words = [](const laspj_var* c) {
+            return c->cells ? (uint32_t)laspj::wpr_of(c->kind, c->E, c->tw) : 0u;
+        };
+        uint32_t c0 = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            laspj_var* v = rq[i].var;
+            const KindState& K = *v->ns;
+            const uint32_t tw = laspj::ktw(K);
+            // the value over the namespace's element slots (new(): zeroed cells); a lazy
+            // threshold's cells are re-laid only when the pairs per element changed (the
+            // namespace went wide since): the slots it does not cover are absent
+            if (K.E)
+                if (int s = laspj::fit_var(ctx, v, K.E, tw)) return s;
+            const laspj_var* t = (*hidden)[i];
+            laspj::ReadDesc& d = hd[i];
+            d.cells = t->cells;
+            d.words = words(t);
+            const uint32_t mode = v->kind == LASPJ_KIND_GSET ? laspj::kReadGset
+                                  : tw > 1                   ? laspj::kReadWide
+                                                             : laspj::kReadNarrow;
+            d.mode_strict = mode << 1 | (rq[i].strict ? 1u : 0u);
+            d.c0 = c0;
+            uint64_t maxw = d.words;
+            hc[c0] = laspj::ReadCur{v->cells, words(v), i};
+            maxw = std::max<uint64_t>(maxw, hc[c0].words);
+            uint32_t nc = 1;
+            if (rq[i].walk)
+                for (laspj::Lazy& z : v->lazy) {
+                    laspj_var* c = z.cells;
+                    if (c->cells && v->kind == LASPJ_KIND_ORSET && c->tw != tw)
+                        if (int s = laspj::fit_var(ctx, c, K.E, tw)) return s;
+                    hc[c0 + nc] = laspj::ReadCur{c->cells, words(c), i};
+                    maxw = std::max<uint64_t>(maxw, hc[c0 + nc].words);
+                    ++nc;
+                }
+            d.nc = nc;
+            c0 += nc;
+            tiles[i] = laspj::read_tiles(maxw);
+        }
+        const uint64_t items = laspj::read_lay_items(hd, n, tiles.data());
+        LJ_HIP(ctx, laspj::launch_read_check(
+                        ctx, reinterpret_cast<const laspj::ReadDesc*>(S->rd_hd), n,
+                        reinterpret_cast<const laspj::ReadCur*>(S->rd_hd + o_cs), ncs, items,
+                        static_cast<uint32_t*>(S->rd_d), S->rd_hd + o_met));
+        launched = true;
+        return LASPJ_OK;
+    };
+    // one run per kind named, each kind's payloads grouped by namespace
+    std::vector<uint32_t> ord[2];
+    for (uint32_t i = 0; i < n; ++i) ord[rq[i].var->kind == LASPJ_KIND_GSET ? 1 : 0].push_back(i);
+    const int last = ord[1].empty() ? 0 : 1;
+    for (int k = 0; k < 2; ++k) {
+        std::vector<uint32_t>& o = ord[k];
+        if (o.empty()) continue;
+        std::stable_sort(o.begin(), o.end(), [&](uint32_t x, uint32_t y) {
+            return std::less<const KindState*>()(rq[x].var->ns.get(), rq[y].var->ns.get());
+        });
+        laspj::Call c;
+        c.op = laspj::Op::WRITE;
+        c.kind = k ? LASPJ_KIND_GSET : LASPJ_KIND_ORSET;
+        c.n = c.m = (uint32_t)o.size();
+        for (uint32_t a = 0; a < o.size(); ++a) {
+            const ReadReq& r = rq[o[a]];
+            c.p.push_back(r.p);
+            c.len.push_back(r.len);
+            c.vars.push_back((*hidden)[o[a]]);
+            if (a == 0 || rq[o[a - 1]].var->ns != r.var->ns)
+                c.groups.push_back(laspj::Group{r.var->ns.get(), a, a + 1});
+            else
+                c.groups.back().p1 = a + 1;
+        }
+        if (k == last) c.tail = tail;
+        std::vector<int32_t> vd;
+        if (int s = laspj::run(ctx, S, c, &vd)) {
+            drop_all();
+            return s;
+        }
+        for (int32_t x : vd)
+            if (x != LASPJ_NIF_OK) {
+                drop_all();                       // (run counted the FALLBACKs)
+                return LASPJ_OK;
+            }
+    }
+    if (!launched || !all_current()) return fallback();
+    const uint8_t* met = static_cast<const uint8_t*>(S->rd_h) + o_met;
+    uint32_t c0 = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t nc = 1 + (rq[i].walk ? (uint32_t)rq[i].var->lazy.size() : 0);
+        (*ans)[i].assign(met + c0, met + c0 + nc);
+        c0 += nc;
+        (*hidden)[i]->image.clear();              // (a reset inside the call wrote cells out)
+    }
+    *verdict = LASPJ_NIF_OK;
+    return LASPJ_OK;
+}
+
+// read_any/3's fold (lasp_core.erl:372-414) over set variables of this context, S->mu held
+// (laspj_var_read is the fold over one pair)
+int read_any_locked(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_var* const* vars,
+                    const uint8_t* const* thresholds, const uint64_t* lens, const int32_t* strict,
+                    uint64_t id, int32_t* found, uint64_t* lazy_ids, uint32_t cap,
+                    uint32_t* nlazy, int32_t* verdict) {
+    *found = -1;
+    for (uint32_t i = 0; i < n; ++i) nlazy[i] = 0;
+    std::vector<ReadReq> rq(n);
+    // the variables named, densely numbered (one may be named again)
+    std::vector<laspj_var*> uniq;
+    std::vector<uint32_t> var_of(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        rq[i] = ReadReq{vars[i], thresholds[i], lens[i], strict[i] ? 1 : 0, true};
+        const auto it = std::find(uniq.begin(), uniq.end(), vars[i]);
+        var_of[i] = (uint32_t)(it - uniq.begin());
+        if (it == uniq.end()) uniq.push_back(vars[i]);
+    }
+    std::vector<laspj_var*> hidden;
+    std::vector<std::vector<uint8_t>> ans;
+    if (int s = read_pass(ctx, S, n, rq.data(), &hidden, &ans, verdict)) return s;
+    if (*verdict != LASPJ_NIF_OK) return LASPJ_OK;
+    auto drop_hidden = [&] {
+        for (laspj_var*& h : hidden) {
+            waiter_cells_drop(S, h);
+            h = nullptr;
+        }
+    };
+    try {
+        std::vector<uint32_t> nl(uniq.size());
+        for (size_t v = 0; v < uniq.size(); ++v) nl[v] = (uint32_t)uniq[v]->lazy.size();
+        std::vector<const uint8_t*> ap(n);
+        for (uint32_t i = 0; i < n; ++i) ap[i] = ans[i].data();
+        laspj::ReadFold f;
+        laspj::read_fold(n, var_of.data(), (uint32_t)uniq.size(), nl.data(), ap.data(), &f);
+        *found = f.found;
+        for (uint32_t i = 0; i < n; ++i) nlazy[i] = (uint32_t)f.fired[i].size();
+        if (f.total > cap || (f.total && !lazy_ids)) {
+            drop_hidden();                        // nothing is changed or registered
+            return LASPJ_OK;
+        }
+        // the waiters built before anything is touched (an allocation may fail)
+        std::vector<laspj::Waiter> ws(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!f.blocked[i]) continue;
+            ws[i].id = id;
+            ws[i].strict = rq[i].strict;
+            ws[i].image.assign(rq[i].p, rq[i].p + rq[i].len);
+            vars[i]->waiters.reserve(vars[i]->waiters.size() + n);
+        }
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t j : f.fired[i]) lazy_ids[at++] = vars[i]->lazy[j].id;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!f.blocked[i]) continue;
+            ws[i].cells = hidden[i];
+            hidden[i] = nullptr;
+            vars[i]->waiters.push_back(std::move(ws[i]));
+        }
+        drop_hidden();                            // the met read's, and those after it
+        for (size_t v = 0; v < uniq.size(); ++v) {
+            std::vector<laspj::Lazy>& lz = uniq[v]->lazy;
+            if (f.still[v].size() == lz.size()) continue;
+            size_t keep = 0, k = 0;
+            for (size_t j = 0; j < lz.size(); ++j) {
+                if (k < f.still[v].size() && f.still[v][k] == j) {
+                    if (keep != j) lz[keep] = std::move(lz[j]);
+                    ++keep;
+                    ++k;
+                } else {
+                    waiter_cells_drop(S, lz[j].cells);
+                }
+            }
+            lz.resize(keep);
+        }
+    } catch (const std::bad_alloc&) {
+        drop_hidden();
+        return fail(ctx, LASPJ_E_NOMEM, "var_read: host allocation");
+    }
+    return LASPJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3101,7 +3433,9 @@ int laspj_var_etf_write(laspj_var* var, const uint8_t* value, uint64_t n, int32_
     if ((!value && n) || !verdict) return fail(ctx, LASPJ_E_INVAL, "var_write: null argument");
     std::lock_guard<std::mutex> lk(S->mu);
     if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_write: unknown variable");
-    return var_write_locked(ctx, S, var, value, n, verdict);
+    const int s = var_write_locked(ctx, S, var, value, n, verdict);
+    if (s == LASPJ_OK) lazy_clear(S, var);
+    return s;
 }
 
 int laspj_var_wait(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
@@ -3249,6 +3583,171 @@ int laspj_var_waiter_at(laspj_var* var, uint32_t k, uint64_t* id, int32_t* stric
     return LASPJ_OK;
 }
 
+int laspj_var_wait_needed(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict,
+                          uint64_t id, int32_t* needed, int32_t* verdict) {
+    if (var && var->gc) {
+        // the entry's threshold is a number, which reply_to_all hands to
+        // riak_dt_gcounter:value/1 as a value (lasp_core.erl:798) and crashes there
+        if (!needed || !verdict) return LASPJ_E_INVAL;
+        *needed = 0;
+        return laspj::gc_refuse(var->gc, verdict);
+    }
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if ((!threshold && n) || !needed || !verdict)
+        return fail(ctx, LASPJ_E_INVAL, "var_wait_needed: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_wait_needed: unknown variable");
+    *needed = 0;
+    const ReadReq rq{var, threshold, n, strict ? 1 : 0, false};
+    std::vector<laspj_var*> hidden;
+    std::vector<std::vector<uint8_t>> ans;
+    if (int s = read_pass(ctx, S, 1, &rq, &hidden, &ans, verdict)) return s;
+    if (*verdict != LASPJ_NIF_OK) return LASPJ_OK;
+    if (ans[0][0] || !var->waiters.empty()) {
+        // met, or somebody is already reading (lasp_core.erl:736-741): ReplyFun(Threshold)
+        waiter_cells_drop(S, hidden[0]);
+        *needed = 1;
+        return LASPJ_OK;
+    }
+    int s = LASPJ_OK;
+    if (strict) {
+        // the entry would hold {strict, T}, which reply_to_all hands to is_inflation as a
+        // value (:798): the reference's clause, and its crash, on the NIF side
+        *verdict = LASPJ_NIF_FALLBACK;
+        ++S->stats[laspj::ST_FALLBACKS];
+    } else {
+        try {
+            laspj::Lazy z;
+            z.id = id;
+            z.image.assign(threshold, threshold + n);
+            z.cells = hidden[0];
+            var->lazy.push_back(std::move(z));
+            return LASPJ_OK;
+        } catch (const std::bad_alloc&) {
+            s = fail(ctx, LASPJ_E_NOMEM, "var_wait_needed: host allocation");
+        }
+    }
+    waiter_cells_drop(S, hidden[0]);
+    return s;
+}
+
+int laspj_var_read(laspj_var* var, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                   int32_t* met, uint64_t* lazy_ids, uint32_t cap, uint32_t* nlazy,
+                   uint32_t* nstill_lazy, int32_t* verdict) {
+    if (var && var->gc) {
+        // laspj_var_wait remains the counter's read
+        if (!met || !nlazy || !nstill_lazy || !verdict) return LASPJ_E_INVAL;
+        *met = 0;
+        *nlazy = *nstill_lazy = 0;
+        return laspj::gc_refuse(var->gc, verdict);
+    }
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if ((!threshold && n) || !met || (!lazy_ids && cap) || !nlazy || !nstill_lazy || !verdict)
+        return fail(ctx, LASPJ_E_INVAL, "var_read: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_read: unknown variable");
+    const int32_t st = strict ? 1 : 0;
+    int32_t found = -1;
+    const int s = read_any_locked(ctx, S, 1, &var, &threshold, &n, &st, id, &found, lazy_ids, cap,
+                                  nlazy, verdict);
+    *met = found == 0 ? 1 : 0;
+    *nstill_lazy = (uint32_t)var->lazy.size();
+    return s;
+}
+
+int laspj_var_read_any(laspj_ctx* ctx, uint32_t n, laspj_var* const* vars,
+                       const uint8_t* const* thresholds, const uint64_t* lens,
+                       const int32_t* strict, uint64_t id, int32_t* found, uint64_t* lazy_ids,
+                       uint32_t cap, uint32_t* nlazy, int32_t* verdict) {
+    if (!ctx) return LASPJ_E_INVAL;
+    if (!found || !verdict) return fail(ctx, LASPJ_E_INVAL, "var_read_any: null argument");
+    *found = -1;
+    *verdict = LASPJ_NIF_OK;
+    if (!n) return LASPJ_OK;                      // lists:foldl over []: not_available_yet
+    if (!vars || !thresholds || !lens || !strict || (!lazy_ids && cap) || !nlazy)
+        return fail(ctx, LASPJ_E_INVAL, "var_read_any: null array");
+    laspj::NifState* S = laspj::state(ctx);
+    if (!S) return fail(ctx, LASPJ_E_NOMEM, "nif: state allocation");
+    std::lock_guard<std::mutex> lk(S->mu);
+    bool counter = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        nlazy[i] = 0;
+        if (vars[i] && vars[i]->gc) {
+            if (laspj::gc_var_ctx(vars[i]->gc) != ctx)
+                return fail(ctx, LASPJ_E_INVAL, "var_read_any: variable %u is not this context's", i);
+            counter = true;
+            continue;
+        }
+        if (!vars[i] || vars[i]->ctx != ctx || !S->vars.count(vars[i]))
+            return fail(ctx, LASPJ_E_INVAL, "var_read_any: variable %u is not this context's", i);
+        if (!thresholds[i] && lens[i])
+            return fail(ctx, LASPJ_E_INVAL, "var_read_any: null threshold");
+    }
+    if (counter) {
+        *verdict = LASPJ_NIF_FALLBACK;
+        ++S->stats[laspj::ST_FALLBACKS];
+        return LASPJ_OK;
+    }
+    return read_any_locked(ctx, S, n, vars, thresholds, lens, strict, id, found, lazy_ids, cap,
+                           nlazy, verdict);
+}
+
+int laspj_var_lazy_count(const laspj_var* var, uint32_t* n) {
+    if (var && var->gc) {
+        if (!n) return LASPJ_E_INVAL;
+        *n = 0;
+        return LASPJ_OK;
+    }
+    laspj::NifState* S = var_state(const_cast<laspj_var*>(var));
+    if (!S || !n) return LASPJ_E_INVAL;
+    std::lock_guard<std::mutex> lk(S->mu);
+    *n = (uint32_t)var->lazy.size();
+    return LASPJ_OK;
+}
+
+int laspj_var_lazy_at(laspj_var* var, uint32_t k, uint64_t* id, const uint8_t** threshold,
+                      uint64_t* n) {
+    if (var && var->gc) return LASPJ_E_RANGE;     // a counter keeps none
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if (!id || !threshold || !n) return fail(ctx, LASPJ_E_INVAL, "var_lazy_at: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (k >= var->lazy.size()) return fail(ctx, LASPJ_E_RANGE, "var_lazy_at: no lazy thread %u", k);
+    const laspj::Lazy& z = var->lazy[k];
+    *id = z.id;
+    *threshold = z.image.data();
+    *n = z.image.size();
+    return LASPJ_OK;
+}
+
+int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found) {
+    if (var && var->gc) {
+        if (!found) return LASPJ_E_INVAL;
+        *found = 0;
+        return LASPJ_OK;
+    }
+    laspj::NifState* S = var_state(var);
+    if (!S) return LASPJ_E_INVAL;
+    laspj_ctx* ctx = var->ctx;
+    if (!found) return fail(ctx, LASPJ_E_INVAL, "var_lazy_cancel: null argument");
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->vars.count(var)) return fail(ctx, LASPJ_E_INVAL, "var_lazy_cancel: unknown variable");
+    *found = 0;
+    for (size_t k = 0; k < var->lazy.size(); ++k)
+        if (var->lazy[k].id == id) {
+            waiter_cells_drop(S, var->lazy[k].cells);
+            var->lazy.erase(var->lazy.begin() + (ptrdiff_t)k);
+            *found = 1;
+            break;
+        }
+    return LASPJ_OK;
+}
+
 int laspj_var_etf_read(laspj_var* var, const uint8_t** out, uint64_t* out_len, int32_t* verdict) {
     if (var && var->gc) return laspj::gc_read(var->gc, false, out, out_len, verdict);
     return var_image_call(var, false, out, out_len, verdict);
@@ -3350,6 +3849,7 @@ int laspj_var_union(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* status,
     laspj::dev_release(ctx, word, 256);
     if (e != hipSuccess) return fail(ctx, LASPJ_E_DEVICE, "var_union: %s", hipGetErrorString(e));
     *status = changed ? LASPJ_BIND_WRITTEN : LASPJ_BIND_NOOP;
+    if (changed) lazy_clear(S, out, true);
     return LASPJ_OK;
 }
 
@@ -3557,6 +4057,7 @@ int laspj_var_etf_update(laspj_var* var, const uint8_t* op, uint64_t nop, int32_
     if (minted) *minted = S->minted.empty() ? nullptr : S->minted.data();
     if (nminted) *nminted = nmint;
     *verdict = LASPJ_NIF_OK;
+    if (*result == LASPJ_UPDATE_OK) lazy_clear(S, var);
     return LASPJ_OK;
 }
 
@@ -3904,6 +4405,7 @@ int filter_run_locked(laspj_ctx* ctx, NifState* S, uint32_t n, laspj_filter* con
         // F's result for some held element is not on the device: out stays as it is
         if (pending[i] == 0 && P.rec[2 * a + 1]) {
             status[i] = LASPJ_BIND_WRITTEN;
+            lazy_clear(S, fs[i]->out, true);
             any = true;
         }
     }
@@ -4203,6 +4705,7 @@ int laspj_var_intersection(laspj_var* out, laspj_var* l, laspj_var* r, int32_t* 
     P.blocks = laspj::proc_blocks(d);
     if (int s = proc_pass(ctx, S, &P, laspj::kProcFused)) return s;
     *status = P.rec[1] ? LASPJ_BIND_WRITTEN : LASPJ_BIND_NOOP;
+    if (P.rec[1]) lazy_clear(S, out, true);
     return LASPJ_OK;
 }
 
