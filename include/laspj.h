@@ -1242,6 +1242,77 @@ int laspj_var_lazy_at(laspj_var* var, uint32_t k, uint64_t* id, const uint8_t** 
  * with that id of `#dv.lazy_threads` (include/lasp.hrl:60-63); *found 0 when there is none */
 int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found);
 
+/* ------------------------------------------------------------------ list-valued resident variables */
+/* A `#dv.value` (include/lasp.hrl:60-63) of type lasp_orset whose value is any list of
+ * {Key, [{Token, Bool}]} — what the combinator bodies bind (lasp_core.erl:460-712: `{X, Cx ++
+ * Cy}`, repeated or reordered keys) — kept on the device between calls as a one-replica
+ * LASPJ_KIND_ORSET_LIST batch.  Its items are the slots of a laspj_var namespace (key =
+ * element slot e, token = 64 e + k, bit 63 the flag): it shares the dictionary of the
+ * canonical variables it is created beside, so their cells feed it without an image, and
+ * nothing is registered per call.  The rank tables the list kernels compare by are derived
+ * on the device from the namespace's images (krank from the element order; grank[64 e + k] =
+ * k's place among element e's tokens: tokens are only compared within one key's runs), fully
+ * after a rebuild of the images and for the patched element slots otherwise.  Keys that are
+ * pairs (product outputs) are not taken.  A dictionary reset (laspj_nif_reset, the 2^20 cap)
+ * or a namespace going wide writes the list out to its image first; after a reset it is
+ * walked back in at its next call, in a wide namespace it stays host-held (read answers the
+ * image, the other calls FALLBACK).  Waiters and lazy threads are not kept for it: the NIF
+ * asks laspj_lvar_etf_threshold per write.  Every call takes the context's call lock, never
+ * the group-commit queue.  After the context is gone every call answers LASPJ_E_INVAL and
+ * destroy still frees. */
+typedef struct laspj_lvar laspj_lvar;
+/* bind/3's third outcome (lasp_core.erl:301-307): merge(Value0, Value) is not an inflation
+ * of Value0, so nothing is written — laspj_list_bind's status 2, which canonical cells never
+ * produce and lists can */
+#define LASPJ_BIND_REFUSED 2
+/* declare/3 (lasp_core.erl:208-218) of a list-valued lasp_orset variable holding [] in
+ * `peer`'s context and namespace; peer must be LASPJ_KIND_ORSET (LASPJ_E_KIND otherwise).
+ * The namespace is shared-owned: peer may be destroyed first. */
+int laspj_lvar_create(laspj_var* peer, laspj_lvar** out);
+/* the `#dv` (include/lasp.hrl:60-63) is dropped: its lists are released, and the namespace
+ * with them when this was its last holder */
+int laspj_lvar_destroy(laspj_lvar* lv);
+/* lasp_core:intersection/7's OR-Set branch (lasp_core.erl:559-568, 583) re-run over resident
+ * variables: for each entry {X, Cx} of l in term order whose key r holds (its cell has any
+ * token, tombstoned or not) the entry {X, Cx ++ Cy}, tokens in term order within Cx and
+ * within Cy with their removed flags; then bind/3 (:291-312) of that AccValue into out:
+ * *status LASPJ_BIND_NOOP, LASPJ_BIND_WRITTEN or LASPJ_BIND_REFUSED.  One fused producer
+ * over the cells and the rank-indexed list bind; nothing crosses PCIe but the status.
+ * verdict FALLBACK, out exactly as it was: l or r is not a current resident OR-Set, the
+ * three are not of one namespace, the namespace is wide, out is held on the host. */
+int laspj_lvar_intersection(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                            int32_t* verdict);
+/* bind/3 (lasp_core.erl:291-312) of any list image (another node's state of this variable):
+ * walked into items over the namespace's dictionary (unseen terms join it as a
+ * laspj_var_etf_bind's do), then laspj_list_bind against the resident list.  verdict
+ * FALLBACK (the registrations undone): an image the walk refuses — not a proper list of
+ * {Key, [{Token, true|false}]}, a key past 64 tokens, `==`-equal terms under two images —,
+ * a wide namespace, a host-held value. */
+int laspj_lvar_etf_bind(laspj_lvar* lv, const uint8_t* value, uint64_t n, int32_t* status,
+                        int32_t* verdict);
+/* write/4 (lasp_core.erl:839-844): the variable := value (verdict FALLBACK: held as the
+ * image on the host) */
+int laspj_lvar_etf_write(laspj_lvar* lv, const uint8_t* value, uint64_t n, int32_t* verdict);
+/* #dv.value as term_to_binary/1 (include/lasp.hrl:60-63; *out valid until the context's
+ * next call) */
+int laspj_lvar_etf_read(laspj_lvar* lv, const uint8_t** out, uint64_t* out_len,
+                        int32_t* verdict);
+/* lasp_orset:value/1 (lasp_orset.erl:67-73) on the list: the keys with a {_, false} token, in
+ * list order, duplicates kept */
+int laspj_lvar_etf_value(laspj_lvar* lv, const uint8_t** out, uint64_t* out_len,
+                         int32_t* verdict);
+/* threshold_met(lasp_orset, #dv.value, Threshold) (lasp_lattice.erl:62-75) on list values:
+ * is_inflation (strict = 0) / is_strict_inflation (strict = 1) of Threshold -> the value, by
+ * laspj_list_inflation (lasp_lattice.erl:137-161, 212-253) */
+int laspj_lvar_etf_threshold(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict,
+                             int32_t* result, int32_t* verdict);
+/* length(#dv.value) and its tokens over all entries (include/lasp.hrl:60-63); a host-held
+ * value: LASPJ_E_UNSUPPORTED */
+int laspj_lvar_counts(laspj_lvar* lv, uint32_t* entries, uint32_t* tokens);
+/* 1 when the value (#dv.value, include/lasp.hrl:60-63) is on the device, 0 when it is held
+ * as an image */
+int laspj_lvar_resident(const laspj_lvar* lv, int32_t* resident);
+
 /* counters of this context's NIF path: [0] calls, [1] device passes, [2] dictionary
  * registrations, [3] dictionary resets, [4] device image rebuilds, [5] host-encoded passes
  * (token images of mixed lengths), [6] FALLBACK verdicts, [7] dictionary elements (both

@@ -93,7 +93,11 @@ extern "C" {
 #define LASPJ_TUNE_LIST_CHUNK   15   /* rows per chunk of the list merges' chunked walk
                                         (0 = default: 1024, or more to keep <= 1024
                                         chunks; 64 .. 2^20)                             */
-int         laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value);
+#define LASPJ_TUNE_LVAR_PRODUCER 16  /* laspj_lvar_intersection's AccValue: 0 = the fused
+                                        producer from both variables' cells, 1 = the
+                                        two-step composition (laspj_list_from_set then
+                                        laspj_list_intersection_set); for A/B            */
+int        laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value);
 
 #ifdef __cplusplus
 }

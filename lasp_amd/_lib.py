@@ -42,7 +42,9 @@ TUNE_ETF_SEG = 9
 TUNE_LIST_WALK = 10
 TUNE_NIF_PASSES = 14
 TUNE_LIST_CHUNK = 15
+TUNE_LVAR_PRODUCER = 16
 NIF_OK, NIF_FALLBACK = 0, 1           # verdicts of the NIF-level entry points
+BIND_NOOP, BIND_WRITTEN, BIND_REFUSED = 0, 1, 2   # bind/3's statuses (REFUSED: lists only)
 NIF_STATS = 20
 GC_NEVER, GC_ALWAYS, GC_T = 0, 1, 2
 
@@ -252,6 +254,17 @@ SIGNATURES = {
     "laspj_filter_args": (i, [vp, vpp, C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_filter_results": (i, [vp, vp, u64]),
     "laspj_var_intersection": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_lvar_create": (i, [vp, vpp]),
+    "laspj_lvar_destroy": (i, [vp]),
+    "laspj_lvar_intersection": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_lvar_etf_bind": (i, [vp, vp, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_lvar_etf_write": (i, [vp, vp, u64, C.POINTER(C.c_int32)]),
+    "laspj_lvar_etf_read": (i, [vp, vpp, C.POINTER(u64), C.POINTER(C.c_int32)]),
+    "laspj_lvar_etf_value": (i, [vp, vpp, C.POINTER(u64), C.POINTER(C.c_int32)]),
+    "laspj_lvar_etf_threshold": (i, [vp, vp, u64, i, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32)]),
+    "laspj_lvar_counts": (i, [vp, C.POINTER(u32), C.POINTER(u32)]),
+    "laspj_lvar_resident": (i, [vp, C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,
                                  C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_increment": (i, [vp, vp, u64, vp, u64, vp, u32, C.POINTER(u32),

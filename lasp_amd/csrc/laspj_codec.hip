@@ -4940,6 +4940,8 @@ bool etf_dict_decodable(const laspj_etf_dict* d) { return d && d->rec_len != 0; 
 bool etf_dict_bin_tokens(const laspj_etf_dict* d) { return d && d->bin_tokens; }
 uint32_t etf_dict_tok_len(const laspj_etf_dict* d) { return d ? d->tok_uniform : 0; }
 uint32_t etf_dict_elements(const laspj_etf_dict* d) { return d ? d->elements : 0; }
+const uint32_t* etf_dict_elem_order(const laspj_etf_dict* d) { return d ? d->elem_order : nullptr; }
+const uint8_t* etf_dict_tok_order(const laspj_etf_dict* d) { return d ? d->tok_order : nullptr; }
 
 void etf_read_plan(const laspj_ctx* ctx, const laspj_etf_dict* d, uint64_t R, const u64* off,
                    EtfReadPlan* plan) {

@@ -39,6 +39,7 @@ struct laspj_ctx {
     int64_t tune_list_walk = 0;
     int64_t tune_nif_passes = 0;     // NIF device passes per call (0: the default)
     int64_t tune_list_chunk = 0;     // rows per chunk of the chunked list walk (0: default)
+    int64_t tune_lvar = 0;           // laspj_lvar_intersection: 1 = the two-step composition
     // device scratch for apply_ops (grown on demand)
     void* scratch = nullptr;
     uint64_t scratch_bytes = 0;
@@ -671,6 +672,50 @@ inline uint64_t read_rec_bytes(uint32_t n, uint32_t ncs) { return 8ull * ncs + 4
 // the context's stream, no synchronisation
 hipError_t launch_read_check(laspj_ctx* ctx, const ReadDesc* rds, uint32_t n, const ReadCur* cs,
                              uint32_t ncs, uint64_t items, uint32_t* rec, uint8_t* met);
+
+// ---- list-valued resident variables (laspj_lvars.hip; include/laspj.h "list-valued
+// resident variables") ---------------------------------------------------------------------
+// the device images the order tables are derived from (laspj_codec.hip): the element slots
+// in term order (E of them, unused slots last) and, per element slot, its token slots in
+// term order (64 bytes, 0xFF after the last; null without tokens)
+const uint32_t* etf_dict_elem_order(const laspj_etf_dict* d);
+const uint8_t* etf_dict_tok_order(const laspj_etf_dict* d);
+// a list batch's arrays as its kernels address them (laspj_lists.hip owns the layout)
+struct ListDev {
+    uint32_t* hdr;                      // [R][2] {entries, tokens}
+    uint64_t* key;                      // [R][ce]
+    uint64_t* tok;                      // [R][ct]
+    uint32_t* toff;                     // [R][ce + 1]
+    uint32_t ce, ct;
+};
+ListDev list_dev(const laspj_batch* b);
+// room for ce entries and ct tokens per replica (ctx->mu held); a batch that grows loses
+// its contents (its known counts become the capacities until it is written)
+int list_reserve(laspj_ctx* ctx, laspj_batch* b, uint32_t ce, uint32_t ct);
+// krank[elem_order[j]] = j and grank[64 e + k] = k's place in row e of tok_order, for every
+// element slot (dirty null) or the ndirty slots listed (device array; krank is untouched:
+// a patch adds no element).  E slots; krank E words, grank 64 E words.
+hipError_t launch_lv_ranks(laspj_ctx* ctx, const uint32_t* elem_order, const uint8_t* tok_order,
+                           uint32_t E, uint32_t* krank, uint32_t* grank, const uint32_t* dirty,
+                           uint32_t ndirty);
+// intersection/7's OR-Set branch (lasp_core.erl:559-568, 583) from two variables' cells: per
+// term-order position j < n, e = elem_order[j]; an entry iff both cells hold a token (cells
+// past El / Er slots are empty); tokens Cx ++ Cy placed by grank.  Two launches, no
+// synchronisation: tile sums into `tiles` (lv_isect_tiles(n) C2 pairs of u64, device), then
+// the writer, whose last tile writes ans = {entries, tokens, overflow} (a host-visible
+// word triple).  overflow 1: out's capacity is short; out is then the empty list.
+struct LvIsect {
+    const uint64_t* l;
+    const uint64_t* r;
+    uint32_t El, Er;
+    const uint32_t* elem_order;
+    uint32_t n;
+    const uint32_t* grank;              // 64 words per element slot
+};
+constexpr uint32_t kLvTile = 1024;      // positions per block: 256 threads x 4
+inline uint32_t lv_isect_tiles(uint32_t n) { return n ? (n + kLvTile - 1) / kLvTile : 1; }
+hipError_t launch_lv_isect(laspj_ctx* ctx, const LvIsect& a, const ListDev& out, uint64_t* tiles,
+                           uint32_t* ans);
 
 // the host's half (laspj_reads_host.cpp: no device, no lock)
 // wave items of a read whose longest block of cells has `words` u64 words

@@ -2446,6 +2446,23 @@ int tiled(laspj_ctx* ctx, laspj_batch* dst, uint64_t max_items, uint64_t pre_byt
 
 }  // namespace
 
+// the layout handed to the list-valued variables' kernels (laspj_lvars.hip)
+namespace laspj {
+
+ListDev list_dev(const laspj_batch* b) {
+    const LV v = view(b);
+    return ListDev{v.hdr, reinterpret_cast<uint64_t*>(v.key), reinterpret_cast<uint64_t*>(v.tok), v.toff,
+                   v.ce, v.ct};
+}
+
+int list_reserve(laspj_ctx* ctx, laspj_batch* b, uint32_t ce, uint32_t ct) {
+    if (ce <= b->cap_e && ct <= b->cap_t) return LASPJ_OK;
+    return list_alloc(ctx, b, ce > b->cap_e ? ce : b->cap_e, ct > b->cap_t ? ct : b->cap_t,
+                      false);
+}
+
+}  // namespace laspj
+
 extern "C" {
 
 int laspj_list_batch_create(laspj_ctx* ctx, int32_t kind, uint64_t replicas,

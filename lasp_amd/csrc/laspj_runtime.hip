@@ -378,6 +378,11 @@ int laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value) {
                 return fail(ctx, LASPJ_E_INVAL, "tuning: list chunk 0 or 64 .. 2^20");
             ctx->tune_list_chunk = value;
             return LASPJ_OK;
+        case LASPJ_TUNE_LVAR_PRODUCER:
+            if (value < 0 || value > 1)
+                return fail(ctx, LASPJ_E_INVAL, "tuning: lvar producer 0 or 1");
+            ctx->tune_lvar = value;
+            return LASPJ_OK;
         default:
             return fail(ctx, LASPJ_E_INVAL, "tuning: unknown knob %d", knob);
     }

@@ -231,6 +231,11 @@ class Context:
         out_var (one namespace), the fun's results kept on the device."""
         return NifFilter(self, in_var, out_var)
 
+    def list_var(self, peer: "NifVar") -> "NifListVar":
+        """laspj_lvar_create: a list-valued lasp_orset variable holding [] in peer's
+        namespace (what the combinator bodies bind: `{X, Cx ++ Cy}`, repeated keys)."""
+        return NifListVar(self, peer)
+
     def filter_run_many(self, filters):
         """laspj_filter_run_many: one re-run of each filter in one device pass —
         [(verdict, status, pending)] per filter."""
@@ -561,6 +566,83 @@ class NifFilter:
     def close(self):
         if self.h:
             self.L.laspj_filter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NifListVar:
+    """laspj_lvar: one list-valued lasp_orset `#dv.value` resident on the device over a
+    NifVar's namespace (laspj.h "list-valued resident variables").  Calls answer (verdict,
+    ...) like the variable calls; bind statuses are 0 no-op, 1 written, 2 refused (the merge
+    does not inflate the value: nothing written)."""
+
+    def __init__(self, ctx: Context, peer: NifVar):
+        self.ctx, self.L = ctx, ctx.L
+        self.h = C.c_void_p()
+        check(self.L.laspj_lvar_create(peer.h, C.byref(self.h)), ctx.h)
+
+    def intersection(self, left: NifVar, right: NifVar):
+        """laspj_lvar_intersection: intersection/7's OR-Set branch over resident left / right
+        bound into this variable — (verdict, status)."""
+        st, verd = C.c_int32(), C.c_int32()
+        check(self.L.laspj_lvar_intersection(self.h, left.h, right.h, C.byref(st),
+                                             C.byref(verd)), self.ctx.h)
+        return int(verd.value), int(st.value)
+
+    def bind(self, img: bytes):
+        """bind/3 of any list image: (verdict, status)."""
+        st, verd = C.c_int32(), C.c_int32()
+        img = bytes(img)
+        check(self.L.laspj_lvar_etf_bind(self.h, img, len(img), C.byref(st), C.byref(verd)),
+              self.ctx.h)
+        return int(verd.value), int(st.value)
+
+    def write(self, img: bytes) -> int:
+        verd = C.c_int32()
+        img = bytes(img)
+        check(self.L.laspj_lvar_etf_write(self.h, img, len(img), C.byref(verd)), self.ctx.h)
+        return int(verd.value)
+
+    def _image(self, fn):
+        out, olen, verd = C.c_void_p(), C.c_uint64(), C.c_int32()
+        check(fn(self.h, C.byref(out), C.byref(olen), C.byref(verd)), self.ctx.h)
+        return int(verd.value), (C.string_at(out, olen.value) if verd.value == 0 else None)
+
+    def read(self):
+        """(verdict, the value's image)."""
+        return self._image(self.L.laspj_lvar_etf_read)
+
+    def value(self):
+        """(verdict, the image of lasp_orset:value/1 on the list)."""
+        return self._image(self.L.laspj_lvar_etf_value)
+
+    def threshold(self, img: bytes, strict: bool = False):
+        res, verd = C.c_int32(), C.c_int32()
+        img = bytes(img)
+        check(self.L.laspj_lvar_etf_threshold(self.h, img, len(img), int(strict),
+                                              C.byref(res), C.byref(verd)), self.ctx.h)
+        return int(verd.value), (bool(res.value) if verd.value == 0 else None)
+
+    def counts(self):
+        """(entries, tokens) of the resident list."""
+        ne, nt = C.c_uint32(), C.c_uint32()
+        check(self.L.laspj_lvar_counts(self.h, C.byref(ne), C.byref(nt)), self.ctx.h)
+        return int(ne.value), int(nt.value)
+
+    @property
+    def resident(self) -> bool:
+        r = C.c_int32()
+        check(self.L.laspj_lvar_resident(self.h, C.byref(r)), self.ctx.h)
+        return bool(r.value)
+
+    def close(self):
+        if self.h:
+            self.L.laspj_lvar_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
