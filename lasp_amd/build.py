@@ -16,7 +16,9 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "liblaspj.so")
 SOURCES = ["laspj_runtime.hip", "laspj_kernels.hip", "laspj_combinators.hip",
            "laspj_codec.hip", "laspj_lists.hip", "laspj_comm.hip",
-           "laspj_many.hip", "laspj_wide.hip", "laspj_nif.hip", "laspj_host.cpp", "laspj_list_etf.cpp",
+           "laspj_many.hip", "laspj_wide.hip", "laspj_nif.hip", "laspj_nif_vars.hip",
+           "laspj_nif_waiters.hip", "laspj_nif_process.hip", "laspj_nif_lvars.hip",
+           "laspj_host.cpp", "laspj_list_etf.cpp",
            "laspj_counters.hip", "laspj_counter_host.cpp", "laspj_process.hip",
            "laspj_reads.hip", "laspj_reads_host.cpp", "laspj_lvars.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -32,10 +34,14 @@ def _jobs() -> int:
     return max(1, min(n, 8, len(SOURCES)))
 
 
+def headers() -> list:
+    """Every header a translation unit may include: a change to any rebuilds them all."""
+    dirs = (CSRC, os.path.join(os.path.dirname(HERE), "include"))
+    return sorted(os.path.join(d, f) for d in dirs for f in os.listdir(d) if f.endswith(".h"))
+
+
 def build(force: bool = False) -> str:
-    headers = [os.path.join(CSRC, "laspj_internal.h"),
-               os.path.join(os.path.dirname(HERE), "include", "laspj.h")]
-    hdr_t = max(os.path.getmtime(h) for h in headers)
+    hdr_t = max(os.path.getmtime(h) for h in headers())
     os.makedirs(OBJ, exist_ok=True)
     objs, todo = [], []
     for s in SOURCES:

@@ -1,6 +1,6 @@
 // riak_dt_gcounter variables resident on the device: the `#dv.value` of the advertisement
 // counter (riak_test/lasp_adcounter_test.erl; include/lasp.hrl:60-63, 76) beside the set
-// variables of laspj_nif.hip, whose entry points branch here for LASPJ_KIND_GCOUNTER.
+// variables of laspj_nif_vars.hip and laspj_nif_waiters.hip, whose entry points branch here for LASPJ_KIND_GCOUNTER.
 //
 // A variable is one row of uint64 counts over the actor slots of its namespace (a host
 // dictionary of element terms, shared by the replicas made with laspj_var_create_replica).

@@ -1463,7 +1463,7 @@ int list_write(const laspj_dict* dict, int32_t kind, const ListItems& it, std::s
 uint32_t list_dict_elements(const laspj_dict* dict) { return (uint32_t)dict->d.elems.size(); }
 
 // ------------------------------------------------------------------ update/3 operations
-// (laspj_nif.hip's laspj_var_etf_update): the Op term of Type:update(Op, Actor, Value0)
+// (laspj_nif_vars.hip's laspj_var_etf_update): the Op term of Type:update(Op, Actor, Value0)
 // read from its image, then its element / token terms registered one by one.
 
 namespace {

@@ -15,7 +15,7 @@
 #include "../../include/laspj_tune.h"
 
 namespace laspj {
-struct NifState;                       // laspj_nif.hip
+struct NifState;                       // laspj_nif_internal.h
 struct ListEtfState;                   // laspj_list_etf.cpp
 void nif_destroy(laspj_ctx* ctx);      // call without ctx->mu held
 }  // namespace laspj
@@ -573,7 +573,7 @@ int gc_threshold_plan(const uint8_t* p, size_t n, bool strict, uint64_t* t);
 
 struct GcVar;                                    // laspj_counters.hip
 struct GcState;                                  // a context's counter variables and staging
-// what the counter path shares with the set path's state (laspj_nif.hip): the context's
+// what the counter path shares with the set path's state (laspj_nif_internal.h): the context's
 // call lock, its laspj_nif_stats counters and the slot its GcState hangs from
 struct GcHooks {
     std::mutex* mu = nullptr;

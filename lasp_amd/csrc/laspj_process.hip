@@ -1,6 +1,6 @@
 // lasp_process re-runs over resident variables (include/laspj.h "resident processes"): the
 // kernels of laspj_filter_run / laspj_filter_run_many / laspj_var_intersection.  The host
-// side (handles, lifecycle, the fun table's host mirror) is in laspj_nif.hip.
+// side (handles, lifecycle, the fun table's host mirror) is in laspj_nif_process.hip.
 //
 // filter/6 (lasp_core.erl:681-712) keeps the entries of `in` whose Function(V) =:= true;
 // the fun's results live beside the variable as two bitmaps over the namespace's element

@@ -1,7 +1,7 @@
 // The read side's check over resident variables (include/laspj.h "lazy threads and
 // one-pass reads"): the kernel of laspj_var_read / laspj_var_read_any /
 // laspj_var_wait_needed.  The host side (hidden cells, lazy lists, the fold of read_any) is
-// in laspj_nif.hip and laspj_reads_host.cpp.
+// in laspj_nif_waiters.hip and laspj_reads_host.cpp.
 //
 // read/6 (lasp_core.erl:331-364) and each step of read_any/3's fold (:371-420) ask, of one
 // threshold T,
@@ -9,7 +9,7 @@
 //   threshold_met(Type, Value, T)                                      (:352)
 // which is is_inflation / is_strict_inflation (lasp_lattice.erl:62-75) with T as the
 // previous state and 1 + L current states: the value and each lazy threshold.  k_waiter_check
-// (laspj_nif.hip) tests many previous states against one current state; this is the
+// (laspj_nif_waiters.hip) tests many previous states against one current state; this is the
 // transpose.  A wave item is one tile of kReadTile 16-byte units of one read: T's two units
 // per lane are loaded once and held in registers, the currents are taken in chunks of
 // kReadChunk (one descriptor per lane, handed round by shuffles), their loads issued four
@@ -32,7 +32,7 @@ namespace {
 
 typedef unsigned long long read2 __attribute__((ext_vector_type(2)));
 
-// unit q of a block of `words` u64 words (as wait_ld of laspj_nif.hip: units past the end
+// unit q of a block of `words` u64 words (as wait_ld of laspj_nif_waiters.hip: units past the end
 // are absent, an odd last word is a unit's first half; null cells have no words)
 __device__ __forceinline__ read2 read_ld(const uint64_t* base, uint64_t q, uint32_t words) {
     read2 v = {0ull, 0ull};
@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(256) k_read_check(const ReadDesc* rds, uint32_
     }
 }
 
-// wait_finish's rule (laspj_nif.hip) with the roles swapped: current j of read i is met when
+// wait_finish's rule (laspj_nif_waiters.hip) with the roles swapped: current j of read i is met when
 // T_i -> C_j is an inflation, strictly so for a strict read
 __global__ void __launch_bounds__(256) k_read_finish(const ReadDesc* rds, const ReadCur* cs,
                                                      uint32_t ncs, uint32_t* rec, uint32_t* np,

@@ -1,6 +1,6 @@
 // The host's half of the one-pass reads (no GPU involved, no lock taken): the wave-item
 // layout of k_read_check's descriptors and the fold of read_any/3 over the met bytes the
-// kernel answered.  laspj_nif.hip builds the descriptors around these and applies the fold
+// kernel answered.  laspj_nif_waiters.hip builds the descriptors around these and applies the fold
 // to the variables' waiter and lazy lists; tests/c/reads_host_check.cpp drives them alone.
 
 #include "laspj_internal.h"

@@ -1,5 +1,5 @@
 """Resident filter processes and the resident G-Set intersection (include/laspj.h "resident
-filter processes"; lasp_amd/csrc/laspj_process.hip, laspj_nif.hip) against filters_model:
+filter processes"; lasp_amd/csrc/laspj_process.hip, laspj_nif_process.hip) against filters_model:
 filter/6 (lasp_core.erl:681-712) re-run over device variables with the fun's results kept
 in two device bitmaps, and intersection/7's G-Set branch (:569-576).  Every case compares
 the output variable's image with the model's bind of the oracle's body."""

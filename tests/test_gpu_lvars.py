@@ -1,5 +1,5 @@
 """List-valued resident variables (include/laspj.h "list-valued resident variables";
-lasp_amd/csrc/laspj_lvars.hip, laspj_nif.hip) against tests/lvars_model.py: intersection/7's
+lasp_amd/csrc/laspj_lvars.hip, laspj_nif_lvars.hip) against tests/lvars_model.py: intersection/7's
 OR-Set branch (lasp_core.erl:559-568, 583) re-run from two resident variables' cells and
 bound with bind/3 (:291-312) into a list held on the device, foreign binds, thresholds and
 the variable's life with its namespace.  Statuses and read() images are compared with the

@@ -1,5 +1,5 @@
 """lasp_core:update/4 on resident variables (laspj_var_etf_update) and per-variable token
-namespaces (include/laspj.h "resident variables"; lasp_amd/csrc/laspj_nif.hip), against the
+namespaces (include/laspj.h "resident variables"; lasp_amd/csrc/laspj_nif_vars.hip), against the
 oracle.
 
 update/4 (lasp_core.erl:283-287) is Type:update(Op, Actor, Value0) then bind/3 of the result:

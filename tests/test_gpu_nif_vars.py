@@ -1,5 +1,5 @@
 """The lasp_gset NIF entry points and the device-resident variables (include/laspj.h
-"NIF entry points", "resident variables"; lasp_amd/csrc/laspj_nif.hip), against the oracle.
+"NIF entry points", "resident variables"; lasp_amd/csrc/laspj_nif.hip, laspj_nif_vars.hip), against the oracle.
 
 G-Set: merge/2 = ordsets:union (lasp_gset.erl:99-101), value/1 = ordsets:to_list
 (:74-76), equal/2 = == (:103-105), is_(strict_)inflation (lasp_lattice.erl:137-140,

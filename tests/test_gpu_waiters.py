@@ -1,5 +1,5 @@
 """Device-resident waiters (include/laspj.h: laspj_var_wait / _recheck / _recheck_many /
-_wait_cancel / _waiter_count / _waiter_at; lasp_amd/csrc/laspj_nif.hip k_waiter_check)
+_wait_cancel / _waiter_count / _waiter_at; lasp_amd/csrc/laspj_nif_waiters.hip k_waiter_check)
 against the reference model of read/6 and reply_to_all/3 (lasp_core.erl:331-364, 765-825)
 in tests/waiters_model.py.  Oracle values are kept as tests/test_gpu_nif_update.py keeps
 them: oorset.update replayed with the device-minted tokens, oorset.merge for binds.
@@ -20,7 +20,7 @@ from waiters_model import FALLBACK, OK, tb
 
 A = Atom
 pytestmark = pytest.mark.gpu
-TILE = 128            # kWaitTile (laspj_nif.hip)
+TILE = 128            # kWaitTile (laspj_nif_waiters.hip)
 
 
 def _ctx():
