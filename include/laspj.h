@@ -1256,10 +1256,12 @@ int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found);
  * pairs (product outputs) are not taken.  A dictionary reset (laspj_nif_reset, the 2^20 cap)
  * or a namespace going wide writes the list out to its image first; after a reset it is
  * walked back in at its next call, in a wide namespace it stays host-held (read answers the
- * image, the other calls FALLBACK).  Waiters and lazy threads are not kept for it: the NIF
- * asks laspj_lvar_etf_threshold per write.  Every call takes the context's call lock, never
- * the group-commit queue.  After the context is gone every call answers LASPJ_E_INVAL and
- * destroy still frees. */
+ * image, the other calls FALLBACK).  Its `#dv.waiting_threads` are kept beside it
+ * (laspj_lvar_wait and the calls after it): a waiter's threshold is walked once into a device
+ * list of its own and all of a variable's waiters are re-checked in one device pass, which
+ * the intersection's re-run can carry inside its own synchronisation.  Lazy threads are not
+ * kept for it.  Every call takes the context's call lock, never the group-commit queue.
+ * After the context is gone every call answers LASPJ_E_INVAL and destroy still frees. */
 typedef struct laspj_lvar laspj_lvar;
 /* bind/3's third outcome (lasp_core.erl:301-307): merge(Value0, Value) is not an inflation
  * of Value0, so nothing is written — laspj_list_bind's status 2, which canonical cells never
@@ -1306,6 +1308,56 @@ int laspj_lvar_etf_value(laspj_lvar* lv, const uint8_t** out, uint64_t* out_len,
  * laspj_list_inflation (lasp_lattice.erl:137-161, 212-253) */
 int laspj_lvar_etf_threshold(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict,
                              int32_t* result, int32_t* verdict);
+/* read/6 with a threshold (lasp_core.erl:331-364) on a list variable: threshold_met(lasp_orset,
+ * #dv.value, Threshold) (lasp_lattice.erl:62-75) answered as laspj_lvar_etf_threshold answers
+ * it, in one pass.  Met -> *met = 1 and nothing is kept; unmet -> *met = 0 and the waiter {id,
+ * strict, Threshold} is appended to `#dv.waiting_threads`: its threshold stays on the device
+ * as the one-replica list the walk made (its items are slots, so the namespace growing leaves
+ * it alone; a dictionary reset makes it stale and it is walked back in from its image at the
+ * variable's next waiter call; a namespace going wide releases it), its image on the host.
+ * verdict FALLBACK, nothing registered and the walk's registrations undone, exactly where
+ * laspj_lvar_etf_threshold answers it: an image the walk refuses, a wide namespace, a
+ * host-held value. */
+int laspj_lvar_wait(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                    int32_t* met, int32_t* verdict);
+/* write/4's reply_to_all (lasp_core.erl:765-825, 839-844) on a list variable, with
+ * laspj_var_recheck's contract: every waiter's threshold checked against the value in one
+ * device pass (lasp_lattice.erl:72-75, 153-161, 235-253: the value's keyfind table built
+ * once, one check launch over all waiters, one finish launch, one synchronisation).
+ * ids[0 .. *nmet) receives the ids of the waiters now met, in list order; they are removed,
+ * the others keep their order (`StillWaiting0 ++ [H]`), *nwaiting of them.  More than cap met:
+ * nothing is removed, *nmet > cap says how much room to come back with.  A variable with no
+ * waiters does no device work.  verdict FALLBACK (a host-held value, a wide namespace):
+ * nothing fires or is removed; the NIF walks the waiters (laspj_lvar_waiter_at), runs the
+ * reference's clause over the read value and cancels those it replied to.  Call it after
+ * laspj_lvar_etf_write and after every bind that answers LASPJ_BIND_WRITTEN: they keep the
+ * waiters (lasp_core.erl:842). */
+int laspj_lvar_recheck(laspj_lvar* lv, uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                       uint32_t* nwaiting, int32_t* verdict);
+/* laspj_lvar_intersection (lasp_core.erl:559-568, 583, 291-312) and, when it answers
+ * LASPJ_BIND_WRITTEN, laspj_lvar_recheck(out) (lasp_core.erl:765-825) in one call: the
+ * answers are exactly those of the two calls.  The check rides behind the bind's last kernel,
+ * against the merge, ahead of the bind's one synchronisation (both lists ascending — every
+ * steady re-run: one device pass instead of two; a list that does not ascend takes the merge
+ * path and the check is enqueued again behind it).  After LASPJ_BIND_NOOP or
+ * LASPJ_BIND_REFUSED the value is unchanged, so no registered waiter can have become met:
+ * *nmet = 0, *nwaiting the waiter count.  verdict FALLBACK with *status LASPJ_BIND_NOOP:
+ * laspj_lvar_intersection's; with *status LASPJ_BIND_WRITTEN: the value was written and the
+ * waiters were not checked (a waiter's image the walk refuses after a dictionary reset). */
+int laspj_lvar_intersection_recheck(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                                    uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                                    uint32_t* nwaiting, int32_t* verdict);
+/* a waiter leaves before it was met (its process died, or the NIF's own walk replied to it:
+ * the first waiter with that id of `#dv.waiting_threads`, include/lasp.hrl:60-63); *found 0
+ * when there is none */
+int laspj_lvar_wait_cancel(laspj_lvar* lv, uint64_t id, int32_t* found);
+/* length(`#dv.waiting_threads`) (include/lasp.hrl:60-63) of a list variable */
+int laspj_lvar_waiter_count(const laspj_lvar* lv, uint32_t* n);
+/* the k-th waiter of a list variable in list order (lasp_core.erl:765-825 walks them so): its
+ * id, strict and its threshold image as registered (valid until the variable's next waiter
+ * call); LASPJ_E_RANGE past the last.  The NIF's walk behind a FALLBACK verdict. */
+int laspj_lvar_waiter_at(laspj_lvar* lv, uint32_t k, uint64_t* id, int32_t* strict,
+                         const uint8_t** threshold, uint64_t* n);
 /* length(#dv.value) and its tokens over all entries (include/lasp.hrl:60-63); a host-held
  * value: LASPJ_E_UNSUPPORTED */
 int laspj_lvar_counts(laspj_lvar* lv, uint32_t* entries, uint32_t* tokens);

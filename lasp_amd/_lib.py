@@ -263,6 +263,16 @@ SIGNATURES = {
     "laspj_lvar_etf_value": (i, [vp, vpp, C.POINTER(u64), C.POINTER(C.c_int32)]),
     "laspj_lvar_etf_threshold": (i, [vp, vp, u64, i, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]),
+    "laspj_lvar_wait": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_lvar_recheck": (i, [vp, vp, u32, C.POINTER(u32), C.POINTER(u32),
+                               C.POINTER(C.c_int32)]),
+    "laspj_lvar_intersection_recheck": (i, [vp, vp, vp, C.POINTER(C.c_int32), vp, u32,
+                                            C.POINTER(u32), C.POINTER(u32),
+                                            C.POINTER(C.c_int32)]),
+    "laspj_lvar_wait_cancel": (i, [vp, u64, C.POINTER(C.c_int32)]),
+    "laspj_lvar_waiter_count": (i, [vp, C.POINTER(u32)]),
+    "laspj_lvar_waiter_at": (i, [vp, u32, C.POINTER(u64), C.POINTER(C.c_int32), vpp,
+                                 C.POINTER(u64)]),
     "laspj_lvar_counts": (i, [vp, C.POINTER(u32), C.POINTER(u32)]),
     "laspj_lvar_resident": (i, [vp, C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,

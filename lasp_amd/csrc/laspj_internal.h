@@ -75,6 +75,15 @@ struct laspj_ctx {
     void* lfi = nullptr;
     uint64_t lfi_bytes = 0;
     uint32_t lf_epoch = 0;
+    // the list variables' waiter check (list_waiters_*): the value's keyfind table, the
+    // waiters' flag words and the error word (device, zeroed by each pass's one memset; a
+    // copy of the descriptors behind them when the pinned ring cannot hold them), and the
+    // answers (pinned, coherent: the finish launch writes the met bytes there)
+    void* lw_dev = nullptr;
+    uint64_t lw_dev_bytes = 0;
+    void* lw_h = nullptr;
+    void* lw_hd = nullptr;          // its device address
+    uint64_t lw_h_bytes = 0;
     // the list merges' chunked walk (k_merge_spec): per-replica round and chunk words,
     // kept zeroed between calls by the kernel's last block per replica
     void* lspec = nullptr;
@@ -692,6 +701,28 @@ ListDev list_dev(const laspj_batch* b);
 // room for ce entries and ct tokens per replica (ctx->mu held); a batch that grows loses
 // its contents (its known counts become the capacities until it is written)
 int list_reserve(laspj_ctx* ctx, laspj_batch* b, uint32_t ce, uint32_t ct);
+// reply_to_all's test (lasp_core.erl:765-825) for the waiters of a list variable: waiter k's
+// threshold is a one-replica OR-Set LIST batch of n entries (the host's count), met[k] =
+// is_inflation (strict: is_strict_inflation) of it -> the value (lasp_lattice.erl:72-75,
+// 153-161, 235-253, as k_linf_probe / k_linf_final restate them).  One pass: a memset, the
+// value's key rank -> first index table built once, one check launch over tiles of kLwTile
+// threshold entries of all waiters, a one-block finish launch that writes the met bytes into
+// pinned memory, one synchronisation.  value: one replica; W >= 1.
+constexpr uint32_t kLwTile = 256;       // threshold entries per work item: one per thread
+struct ListWaiter {
+    const laspj_batch* list;
+    uint32_t n;
+    uint32_t strict;
+};
+int list_waiters_check(laspj_ctx* ctx, const laspj_batch* value, const laspj_list_order* ord,
+                       const ListWaiter* ws, uint32_t W, uint8_t* met);
+// laspj_list_bind of one-replica lists with a tail: the check pass of ws against dst (the
+// merge) enqueued behind the bind's last kernel and ahead of its one synchronisation (again
+// behind the merge path when the rank-indexed bind answers retry); met is written only when
+// *status comes back 1 (written).  ws null: laspj_list_bind.
+int list_bind_tail(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
+                   const laspj_batch* val, const laspj_list_order* ord, uint8_t* status,
+                   const ListWaiter* ws, uint32_t W, uint8_t* met);
 // krank[elem_order[j]] = j and grank[64 e + k] = k's place in row e of tok_order, for every
 // element slot (dirty null) or the ndirty slots listed (device array; krank is untouched:
 // a patch adds no element).  E slots; krank E words, grank 64 E words.

@@ -1725,6 +1725,127 @@ __global__ void k_linf_final(LV prev, LV cur, bool bcast, uint64_t R, const uint
     }
 }
 
+// ---------------------------------------------------------------- a list variable's waiters
+// reply_to_all's test (lasp_core.erl:765-825) for every waiter of one list-valued variable:
+// threshold_met(lasp_orset, Value, T) is is_inflation(T, Value), is_strict_inflation for
+// {strict, T} (lasp_lattice.erl:72-75), the OR-Set clauses above with Prev = the waiter's
+// threshold and Cur = the value.  The value's table is built once (k_lw_insert: h_insert
+// keeps the smallest index, keyfind's first match), then one launch checks every waiter: a
+// work item is one tile of kLwTile entries of one waiter's threshold (a block finds its
+// waiter by binary search over item0, as k_proc_many does), a thread does k_linf_probe's
+// OR-Set branch for its entry, a wave ORs its bits and issues at most one atomic.  The
+// one-block finish launch behind it applies k_linf_final's rule per waiter — a waiter with
+// no entries has no item and is answered there — and writes the met bytes into pinned
+// memory.  No wave waits for another: the launches are ordered by the stream.
+//
+// The pass also rides behind a bind (list_bind_tail), where the value is the merge the bind
+// has just written: its length is then known on the device only, so the table is sized from
+// the host's bound `ub` and every count and token offset read from the value is clamped to
+// the list's capacity.  skip (or null): a device word that is non-zero when the bind wrote
+// no merge at all (the rank-indexed bind's retry): the pass then touches nothing.
+struct LwDesc {
+    const u64* key;
+    const u64* tok;
+    const uint32_t* toff;
+    uint32_t n;                 // the threshold's entries
+    uint32_t strict;
+};
+static_assert(sizeof(LwDesc) == 32, "descriptor layout");
+
+struct LwPass {
+    const LwDesc* w;            // W descriptors
+    const uint32_t* item0;      // W + 1: waiter k's first work item; item0[W] = the items
+    uint32_t W;
+    uint32_t ub;                // the value holds at most this many entries (<= val.ce)
+    u64* hk;                    // the value's table: hsize slots, zero on entry
+    uint32_t* hi;
+    uint32_t hsize;
+    uint32_t* flags;            // W words, zero on entry
+    const uint32_t* skip;
+    uint8_t* met;               // W bytes (pinned)
+    uint32_t* err_out;          // rk.flag's word copied beside them
+};
+
+__device__ __forceinline__ uint32_t lw_count(const LV& val, uint32_t ub) {
+    const uint32_t n = val.hdr[0];
+    return n < ub ? n : ub;
+}
+
+__global__ __launch_bounds__(256) void k_lw_insert(LV val, RK rk, LwPass p) {
+    if (p.skip && *p.skip) return;
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < lw_count(val, p.ub)) h_insert(p.hk, p.hi, p.hsize - 1, key_ord(val.key[i], rk), i);
+}
+
+__global__ __launch_bounds__(kLwTile) void k_lw_check(LV val, RK rk, LwPass p) {
+    if (p.skip && *p.skip) return;
+    // the waiter of this item: the last one whose first item is not past it (a waiter with
+    // no entries has no item: item0[k] == item0[k + 1])
+    const uint32_t item = blockIdx.x;
+    uint32_t lo = 0, hi = p.W;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (p.item0[mid] <= item) lo = mid;
+        else hi = mid;
+    }
+    const LwDesc d = p.w[lo];
+    const uint32_t i = (item - p.item0[lo]) * kLwTile + threadIdx.x;
+    const uint32_t nc = lw_count(val, p.ub);
+    bool viol = false, changed = false;
+    if (i < d.n) {
+        // lists:keyfind(Element, 1, Current): the first entry with an equal key
+        const uint32_t j = h_find(p.hk, p.hi, p.hsize - 1, key_ord(d.key[i], rk));
+        if (j == kNone || j >= nc) {
+            viol = true;
+        } else {
+            const u64* tp = d.tok + d.toff[i];
+            const uint32_t lp = d.toff[i + 1] - d.toff[i];
+            uint32_t c1 = val.toff[j + 1], c0 = val.toff[j];
+            c1 = c1 < val.ct ? c1 : val.ct;
+            c0 = c0 < c1 ? c0 : c1;
+            const u64* tc = val.tok + c0;
+            const uint32_t lc = c1 - c0;
+            // ids_inflated: every threshold token keyfind-s among the value's (flags ignored)
+            for (uint32_t x = 0; x < lp && !viol; ++x) {
+                const u64 ox = tok_ord(tp[x], rk);
+                bool found = false;
+                for (uint32_t y = 0; y < lc && !found; ++y) found = tok_ord(tc[y], rk) == ox;
+                viol = !found;
+            }
+            // DeletedElements: Ids =/= Ids1 (order- and flag-sensitive)
+            if (d.strict) {
+                if (lp != lc) {
+                    changed = true;
+                } else {
+                    for (uint32_t x = 0; x < lp && !changed; ++x)
+                        changed = tok_ord(tp[x], rk) != tok_ord(tc[x], rk) ||
+                                  ((tp[x] ^ tc[x]) & kRemoved) != 0;
+                }
+            }
+        }
+    }
+    const uint32_t f = (viol ? kViolBit : 0u) | (changed ? kChangedBit : 0u);
+    const u64 any = __ballot(f != 0);
+    uint32_t wf = f;
+    for (int off = 32; off > 0; off >>= 1) wf |= __shfl_xor(wf, off, 64);
+    if (any && lane_id() == 0) atomicOr(p.flags + lo, wf);
+}
+
+__global__ __launch_bounds__(256) void k_lw_finish(LV val, RK rk, LwPass p) {
+    if (p.skip && *p.skip) return;
+    const uint32_t nc = lw_count(val, p.ub);
+    for (uint32_t k = threadIdx.x; k < p.W; k += 256) {
+        const uint32_t np = p.w[k].n, f = p.flags[k];
+        bool res = !(f & kViolBit);
+        if (p.w[k].strict) {
+            if (np == 0 && nc != 0) res = true;            // ([], Current) when Current =/= []
+            else res = res && ((f & kChangedBit) != 0 || np < nc);   // NewElements: length/1
+        }
+        p.met[k] = res ? 1 : 0;
+    }
+    if (threadIdx.x == 0) *p.err_out = *rk.flag;
+}
+
 // ---------------------------------------------------------------- tiled producers
 // Every producer below emits, per replica, a compaction of one input sequence in order:
 // item i of replica r emits ne_i entries and nt_i tokens at the exclusive prefix sums of
@@ -3044,13 +3165,138 @@ static int grow_block(laspj_ctx* ctx, void** p, uint64_t* have, uint64_t bytes, 
     return LASPJ_OK;
 }
 
+// the met bytes and the error word of W waiters in the pass's pinned block
+static uint64_t lw_err_at(uint32_t W) { return ((uint64_t)W + 3) & ~3ull; }
+
+// The waiter check of ws against `value` enqueued on the context's stream (ctx->mu held): a
+// memset of the pass's own zeroed block, k_lw_insert, k_lw_check, k_lw_finish.  ub_e: the
+// value holds at most that many entries (its table is sized from it).  The descriptors go
+// through the context's pinned ring and are read in place.
+static int list_waiters_enqueue(laspj_ctx* ctx, const laspj_batch* value, uint64_t ub_e, RK rk,
+                                const ListWaiter* ws, uint32_t W, const uint32_t* skip,
+                                const char* what) {
+    if (!W || value->replicas != 1 || value->kind != LASPJ_KIND_ORSET_LIST)
+        return fail(ctx, LASPJ_E_INVAL, "%s: waiters of a one-replica OR-Set list", what);
+    const uint32_t ub = (uint32_t)std::min<uint64_t>(ub_e, value->cap_e);
+    const uint32_t hsize = pow2_at_least(2ull * std::max(ub, 1u));
+    // descriptors: [LwDesc x W | item0 x (W + 1)]
+    const uint64_t dbytes = 32ull * W + 4ull * (W + 1ull);
+    std::vector<uint8_t> blob(dbytes);
+    auto* hd = reinterpret_cast<LwDesc*>(blob.data());
+    auto* hitem = reinterpret_cast<uint32_t*>(blob.data() + 32ull * W);
+    uint64_t items = 0;
+    for (uint32_t k = 0; k < W; ++k) {
+        const laspj_batch* b = ws[k].list;
+        if (!b || b->ctx != ctx || b->kind != LASPJ_KIND_ORSET_LIST || b->replicas != 1 ||
+            ws[k].n > b->cap_e)
+            return fail(ctx, LASPJ_E_INVAL, "%s: waiter %u's list", what, k);
+        const LV v = view(b);
+        hd[k] = LwDesc{v.key, v.tok, v.toff, ws[k].n, ws[k].strict ? 1u : 0u};
+        hitem[k] = (uint32_t)items;
+        items += (ws[k].n + kLwTile - 1) / kLwTile;
+        if (items > 0x7FFFFFFFull) return fail(ctx, LASPJ_E_RANGE, "%s: thresholds too long", what);
+    }
+    hitem[W] = (uint32_t)items;
+    // device: [table keys 8 hsize | first indices 4 hsize | flags 4 W | error word], zeroed
+    // (to a multiple of 256 bytes: one fill kernel), then room for the descriptors
+    const uint64_t o_hi = 8ull * hsize, o_fl = o_hi + 4ull * hsize, o_err = o_fl + 4ull * W;
+    const uint64_t zbytes = (o_err + 4 + 255) & ~255ull;
+    if (int s = grow_block(ctx, &ctx->lw_dev, &ctx->lw_dev_bytes, zbytes + ((dbytes + 255) & ~255ull),
+                           false, what))
+        return s;
+    const uint64_t hbytes = lw_err_at(W) + 4;
+    if (ctx->lw_h_bytes < hbytes) {
+        if (ctx->lw_h) {
+            hipStreamSynchronize(ctx->stream);
+            hipHostFree(ctx->lw_h);
+            ctx->lw_h = nullptr;
+            ctx->lw_h_bytes = 0;
+        }
+        const uint64_t want = std::max<uint64_t>(hbytes, 4096);
+        if (hipHostMalloc(&ctx->lw_h, want, hipHostMallocCoherent) != hipSuccess) {
+            hipGetLastError();
+            ctx->lw_h = nullptr;
+            return fail(ctx, LASPJ_E_NOMEM, "%s: pinned answers", what);
+        }
+        ctx->lw_h_bytes = want;
+        LJ_HIP(ctx, hipHostGetDevicePointer(&ctx->lw_hd, ctx->lw_h, 0));
+    }
+    char* base = static_cast<char*>(ctx->lw_dev);
+    const char* ddev = nullptr;
+    if (const void* slot = laspj::stage_small(ctx, blob.data(), dbytes))
+        ddev = static_cast<const char*>(laspj::staged_dev(ctx, slot));
+    if (!ddev) {
+        // too many for the ring: copied behind the zeroed block, and landed before `blob` goes
+        LJ_HIP(ctx, hipMemcpyAsync(base + zbytes, blob.data(), dbytes, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ddev = base + zbytes;
+    }
+    LJ_HIP(ctx, hipMemsetAsync(base, 0, zbytes, ctx->stream));
+    LwPass p;
+    p.w = reinterpret_cast<const LwDesc*>(ddev);
+    p.item0 = reinterpret_cast<const uint32_t*>(ddev + 32ull * W);
+    p.W = W;
+    p.ub = ub;
+    p.hk = reinterpret_cast<u64*>(base);
+    p.hi = reinterpret_cast<uint32_t*>(base + o_hi);
+    p.hsize = hsize;
+    p.flags = reinterpret_cast<uint32_t*>(base + o_fl);
+    p.skip = skip;
+    p.met = static_cast<uint8_t*>(ctx->lw_hd);
+    p.err_out = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->lw_hd) + lw_err_at(W));
+    rk.flag = reinterpret_cast<uint32_t*>(base + o_err);
+    const LV val = view(value);
+    hipLaunchKernelGGL(k_lw_insert, dim3(std::max(1u, (ub + 255) / 256)), dim3(256), 0,
+                       ctx->stream, val, rk, p);
+    if (items)
+        hipLaunchKernelGGL(k_lw_check, dim3((unsigned)items), dim3(kLwTile), 0, ctx->stream, val,
+                           rk, p);
+    hipLaunchKernelGGL(k_lw_finish, dim3(1), dim3(256), 0, ctx->stream, val, rk, p);
+    LJ_LAUNCHED(ctx);
+    return LASPJ_OK;
+}
+
+// after the stream's synchronisation: the pass's error word, then its met bytes
+static int list_waiters_answer(laspj_ctx* ctx, uint32_t W, uint8_t* met, const char* what) {
+    const auto* h = static_cast<const uint8_t*>(ctx->lw_h);
+    uint32_t f = 0;
+    std::memcpy(&f, h + lw_err_at(W), 4);
+    if (int s = flag_status(ctx, f, what)) return s;
+    std::memcpy(met, h, W);
+    return LASPJ_OK;
+}
+
+}  // extern "C"
+
+namespace laspj {
+
+int list_waiters_check(laspj_ctx* ctx, const laspj_batch* value, const laspj_list_order* ord,
+                       const ListWaiter* ws, uint32_t W, uint8_t* met) {
+    if (int s = check_list(ctx, value, "list_waiters")) return s;
+    if (!ws || !met) return fail(ctx, LASPJ_E_INVAL, "list_waiters: null argument");
+    RK rk;
+    if (int s = ranks(ctx, ord, true, &rk, "list_waiters")) return s;
+    LGuard g(ctx);
+    if (int s = list_waiters_enqueue(ctx, value, value->known_e, rk, ws, W, nullptr,
+                                     "list_waiters"))
+        return s;
+    LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return list_waiters_answer(ctx, W, met, "list_waiters");
+}
+
+}  // namespace laspj
+
+extern "C" {
+
 constexpr int kLfRetry = 1;     // list_bind_ascending: take the merge path instead
 
 // list_bind over the rank universe when both lists' keys strictly ascend (k_lbf_*):
 // LASPJ_OK with status / dst set, kLfRetry when a replica does not ascend (the lists are
 // marked not_asc, so the next bind of them goes straight to the merge path), or an error
 static int list_bind_ascending(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
-                               const laspj_batch* val, const RK& rk, uint8_t* status) {
+                               const laspj_batch* val, const RK& rk, uint8_t* status,
+                               const ListWaiter* ws, uint32_t W) {
     const bool gs = cur->kind == LASPJ_KIND_GSET_LIST;
     const uint64_t R = cur->replicas, nk = rk.nk;
     const uint64_t be = (uint64_t)cur->known_e + val->known_e;
@@ -3109,6 +3355,10 @@ static int list_bind_ascending(laspj_ctx* ctx, laspj_batch* dst, const laspj_bat
     if (hipGetLastError() != hipSuccess) return fail(ctx, LASPJ_E_DEVICE, "list_bind: launch");
     ctx->lf_parity = par;
     ctx->lf_prev_use = use;
+    // the tail: the waiters against the merge (at most `be` entries); a replica that answers
+    // retry wrote no merge, and its `bad` word says so to the tail's kernels
+    if (ws)
+        if (int s = list_waiters_enqueue(ctx, dst, be, rk, ws, W, f.w + R, "list_bind")) return s;
     const hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess)
         return fail(ctx, LASPJ_E_DEVICE, "list_bind: synchronise: %s", hipGetErrorString(e));
@@ -3131,6 +3381,14 @@ static int list_bind_ascending(laspj_ctx* ctx, laspj_batch* dst, const laspj_bat
 
 int laspj_list_bind(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
                     const laspj_batch* val, const laspj_list_order* ord, uint8_t* status) {
+    return laspj::list_bind_tail(ctx, dst, cur, val, ord, status, nullptr, 0, nullptr);
+}
+
+}  // extern "C"
+
+int laspj::list_bind_tail(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
+                          const laspj_batch* val, const laspj_list_order* ord, uint8_t* status,
+                          const ListWaiter* ws, uint32_t W, uint8_t* met) {
     if (int s = check_list(ctx, dst, "list_bind")) return s;
     if (int s = check_list(ctx, cur, "list_bind")) return s;
     if (int s = check_list(ctx, val, "list_bind")) return s;
@@ -3139,6 +3397,8 @@ int laspj_list_bind(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
     RK rk;
     if (int s = ranks(ctx, ord, cur->kind != LASPJ_KIND_GSET_LIST, &rk, "list_bind")) return s;
     const uint64_t R = cur->replicas;
+    if (ws && (R != 1 || !W || !met))
+        return fail(ctx, LASPJ_E_INVAL, "list_bind: a tail takes one replica and its waiters");
     LGuard g(ctx);
     // both lists ascending (tried unless a list is known not to, and while the rank universe
     // is not much larger than the lists): the rank-indexed bind, two launches
@@ -3147,7 +3407,9 @@ int laspj_list_bind(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
         rk.nk <= 16ull * ((uint64_t)cur->known_e + val->known_e) + 65536 &&
         (uint64_t)cur->known_e + val->known_e < (1ull << 30) &&
         (uint64_t)cur->known_t + val->known_t <= 0xFFFFFFF0ull) {
-        const int s = list_bind_ascending(ctx, dst, cur, val, rk, status);
+        const int s = list_bind_ascending(ctx, dst, cur, val, rk, status, ws, W);
+        if (s == LASPJ_OK && ws && status[0] == 1)
+            return list_waiters_answer(ctx, W, met, "list_bind");
         if (s != kLfRetry) return s;
     }
     // the context's bind block (device): [words 4R + 4 (BindFin): the error word the
@@ -3222,6 +3484,9 @@ int laspj_list_bind(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
             ctx->ltab_dirty = false;          // the clean-ups are enqueued
             ctx->lbind_dirty = false;
         }
+        // the tail behind the answer's kernel: the waiters against the merge
+        if (s == LASPJ_OK && ws)
+            s = list_waiters_enqueue(ctx, dst, be, rk, ws, W, nullptr, "list_bind");
     }
     const auto* hb = static_cast<const uint8_t*>(ctx->lbind_h);
     if (s == LASPJ_OK) {
@@ -3240,8 +3505,11 @@ int laspj_list_bind(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* cur,
     set_known(dst, reinterpret_cast<const uint32_t*>(hb), R);
     // status: 0 = cur =:= val (no-op), 1 = the merge inflates cur (written), 2 = it does not
     std::memcpy(status, hb + 8 * R, R);
+    if (ws && status[0] == 1) return list_waiters_answer(ctx, W, met, "list_bind");
     return LASPJ_OK;
 }
+
+extern "C" {
 
 int laspj_list_value(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* src) {
     if (int s = check_list(ctx, dst, "list_value")) return s;

@@ -1628,6 +1628,7 @@ void nif_destroy(laspj_ctx* ctx) {
                 if (*b) laspj_batch_destroy(*b);
                 *b = nullptr;
             }
+            for (LWaiter& w : lv->waiters) lwaiter_release(w);
             free_ns(*lv->ns);
             lv->ns->lvars.clear();
             lv->ctx = nullptr;

@@ -84,6 +84,21 @@ struct Waiter {
     laspj_var* cells = nullptr;
 };
 
+// One entry of a list-valued variable's `#dv.waiting_threads`: the threshold walked once over
+// the variable's namespace into a one-replica OR-Set LIST batch of its own (its items are
+// slots, so the namespace growing leaves it alone), and its image as registered.  `list` is
+// null while the threshold is not on the device: a dictionary reset made its items stale
+// (walked back in from the image at the variable's next waiter call; `epoch` names the
+// generation the items refer to) or the namespace went wide (it stays out).
+struct LWaiter {
+    uint64_t id = 0;
+    int32_t strict = 0;
+    std::vector<uint8_t> image;
+    laspj_batch* list = nullptr;
+    uint32_t n = 0;                  // the threshold's entries
+    uint64_t epoch = 0;
+};
+
 }  // namespace laspj
 
 // A device-resident variable's value (the `#dv.value` of lasp_core's store): cells over its
@@ -148,6 +163,7 @@ struct laspj_lvar {
     laspj_batch* dst = nullptr;
     laspj_batch* tmp = nullptr;      // l's list form (the two-step composition, A/B only)
     std::vector<uint8_t> image;
+    std::vector<laspj::LWaiter> waiters;   // `#dv.waiting_threads`, in list order
 };
 
 namespace laspj {
@@ -411,6 +427,8 @@ void waiter_cells_drop(NifState* S, laspj_var* c);
 // ---- laspj_nif_lvars.hip ----------------------------------------------------------------
 // the namespace's resident lists written out to their images (S->mu held, ctx->mu not)
 int spill_lvars(NifState* S, KindState& K);
+// a list variable's waiter gives its device list back, its image stays (the context alive)
+void lwaiter_release(LWaiter& w);
 
 // ---- what the entry points open and close with ------------------------------------------
 // An entry point's opening: the handle's context state, the null-argument check, the call

@@ -2,7 +2,9 @@
 // include/laspj.h "list-valued resident variables": a `#dv.value` that is any list of
 // {Key, [{Token, Bool}]}, kept as a LIST batch over the slots of a laspj_var namespace.  The
 // list kernels are laspj_lists.hip's; the order tables and the producer of intersection/7's
-// OR-Set branch (lasp_core.erl:559-568, 583) are laspj_lvars.hip's.
+// OR-Set branch (lasp_core.erl:559-568, 583) are laspj_lvars.hip's.  The variable's waiting
+// threads (read/6 and write/4's reply_to_all, lasp_core.erl:331-364, 765-825) are kept here as
+// device lists and checked by laspj_lists.hip's waiter pass, alone or behind a bind.
 
 #include "laspj_nif_internal.h"
 
@@ -10,6 +12,12 @@ using laspj::fail;
 using laspj::var_state;
 
 namespace laspj {
+
+void lwaiter_release(LWaiter& w) {
+    if (w.list) laspj_batch_destroy(w.list);
+    w.list = nullptr;
+}
+
 namespace {
 
 // the list of a one-replica batch as items (list order)
@@ -177,11 +185,17 @@ int lvar_prepare(laspj_ctx* ctx, NifState* S, KindState& K) {
 
 // bind/3 (lasp_core.erl:291-312) of lv->val into the variable: laspj_list_bind's status; the
 // merge becomes the variable's list by a swap of the two batches when it is written
-int lvar_bind(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, int32_t* status) {
+// tail (or null): the variable's waiters checked against the merge inside the bind's one
+// synchronisation (list_bind_tail); met: a byte per waiter, written when the status is 1
+int lvar_bind(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, int32_t* status,
+              const std::vector<ListWaiter>* tail = nullptr, uint8_t* met = nullptr) {
     const LvOrder ord(ctx, *lv->ns);
     uint8_t st = 0;
     const uint64_t t0 = now_ns();
-    if (int s = laspj_list_bind(ctx, lv->dst, lv->list, lv->val, &ord.o, &st)) return s;
+    if (int s = list_bind_tail(ctx, lv->dst, lv->list, lv->val, &ord.o, &st,
+                               tail ? tail->data() : nullptr, tail ? (uint32_t)tail->size() : 0,
+                               met))
+        return s;
     ++S->stats[ST_PASSES];
     S->stats[ST_NS_WAIT] += now_ns() - t0;
     if (st == 1) std::swap(lv->list, lv->dst);
@@ -211,7 +225,9 @@ int lvar_scratch(laspj_ctx* ctx, NifState* S, uint32_t ntile) {
 
 // laspj_lvar_intersection with S->mu held and the handles checked
 int lvar_intersection_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj_var* l,
-                             laspj_var* r, int32_t* status, int32_t* verdict) {
+                             laspj_var* r, int32_t* status, int32_t* verdict,
+                             const std::vector<ListWaiter>* tail = nullptr,
+                             uint8_t* met = nullptr) {
     ++S->stats[ST_CALLS];
     *status = LASPJ_BIND_NOOP;
     *verdict = LASPJ_NIF_FALLBACK;
@@ -284,7 +300,7 @@ int lvar_intersection_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj
     }
     S->stats[ST_NS_ENQUEUE] += now_ns() - t0;
     int32_t st = 0;
-    if (int s = lvar_bind(ctx, S, out, &st)) return s;
+    if (int s = lvar_bind(ctx, S, out, &st, tail, met)) return s;
     if (ctx->tune_lvar != 1) {
         if (S->lv_ans[2] != 0)
             return fail(ctx, LASPJ_E_RANGE, "lvar_intersection: the producer's output bound did "
@@ -318,11 +334,77 @@ int lvar_walk_val(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, const uint8_t* p,
     return LASPJ_OK;
 }
 
+// *ok: every waiter's threshold is on the device over the current dictionary.  One whose
+// list a dictionary reset made stale is walked back in from its image here (its terms
+// registered afresh: the caller brings the images and tables up to them); in a wide
+// namespace, or when the walk refuses an image, the lists stay as they are.  S->mu held.
+int lwaiters_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
+    KindState& K = *lv->ns;
+    *ok = !K.wide;
+    if (K.wide) return LASPJ_OK;
+    for (LWaiter& w : lv->waiters) {
+        if (w.list && w.epoch == K.epoch) continue;
+        if (!K.dict)
+            if (int s = reset_dict(ctx, S, K)) return s;
+        const RegMark m = reg_mark(K);
+        ListItems it;
+        const int st = list_walk(K.dict, LASPJ_KIND_ORSET, w.image.data(), w.image.size(), &it,
+                                 nullptr);
+        if (st == LASPJ_E_NOMEM) return fail(ctx, LASPJ_E_NOMEM, "lvar: host allocation");
+        if (st != LASPJ_DEC_OK) {
+            *ok = false;
+            return LASPJ_OK;
+        }
+        reg_note(S, K, m);
+        if (!w.list)
+            if (int s = laspj_list_batch_create(ctx, LASPJ_KIND_ORSET_LIST, 1, 1, 1, &w.list))
+                return s;
+        if (int s = lvar_upload(ctx, w.list, it)) return s;
+        w.n = (uint32_t)it.keys.size();
+        w.epoch = K.epoch;
+        ++S->stats[ST_HYDRATED];
+    }
+    return LASPJ_OK;
+}
+
+// the waiters as the check pass takes them, in list order
+std::vector<ListWaiter> lwaiter_descs(const laspj_lvar* lv) {
+    std::vector<ListWaiter> d;
+    d.reserve(lv->waiters.size());
+    for (const LWaiter& w : lv->waiters) d.push_back(ListWaiter{w.list, w.n, (uint32_t)w.strict});
+    return d;
+}
+
+// reply_to_all's outcome (lasp_core.erl:795-825): the met waiters' ids in list order,
+// removed — the others keep their order — unless more than cap are met
+void lwaiters_take(laspj_lvar* lv, const uint8_t* met, uint64_t* ids, uint32_t cap,
+                   uint32_t* nmet) {
+    std::vector<LWaiter>& ws = lv->waiters;
+    uint32_t total = 0;
+    for (size_t k = 0; k < ws.size(); ++k) total += met[k] ? 1u : 0u;
+    *nmet = total;
+    if (!total || total > cap || !ids) return;
+    size_t keep = 0, at = 0;
+    for (size_t k = 0; k < ws.size(); ++k) {
+        if (met[k]) {
+            ids[at++] = ws[k].id;
+            lwaiter_release(ws[k]);
+        } else {
+            if (keep != k) ws[keep] = std::move(ws[k]);
+            ++keep;
+        }
+    }
+    ws.resize(keep);
+}
+
 }  // namespace
 
 int spill_lvars(NifState* S, KindState& K) {
-    for (laspj_lvar* lv : K.lvars)
+    for (laspj_lvar* lv : K.lvars) {
         if (int s = lvar_spill(S, lv)) return s;
+        // the waiters' lists name the same slots: released, their images kept
+        for (LWaiter& w : lv->waiters) lwaiter_release(w);
+    }
     return LASPJ_OK;
 }
 
@@ -351,6 +433,7 @@ void lvar_free_batches(laspj_lvar* lv) {
         if (*b) laspj_batch_destroy(*b);
         *b = nullptr;
     }
+    for (laspj::LWaiter& w : lv->waiters) laspj::lwaiter_release(w);
 }
 
 }  // namespace
@@ -588,6 +671,179 @@ int laspj_lvar_etf_threshold(laspj_lvar* lv, const uint8_t* threshold, uint64_t 
         *verdict = LASPJ_NIF_OK;
         return LASPJ_OK;
     });
+}
+
+int laspj_lvar_wait(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                    int32_t* met, int32_t* verdict) {
+    const laspj::Entry e = enter_lvar(lv, "lvar_wait", threshold && n && met && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    ++S->stats[laspj::ST_CALLS];
+    *met = 0;
+    *verdict = LASPJ_NIF_FALLBACK;
+    return laspj::nomem_guard(ctx, "lvar_wait", [&]() -> int {
+        bool ok = false, wok = false;
+        if (int s = laspj::lvar_ready(ctx, S, lv, &ok)) return s;
+        // (stale waiters come back ahead of the threshold's walk, which brings the images up
+        // to every term registered; one the walk refuses waits for recheck's FALLBACK)
+        if (ok)
+            if (int s = laspj::lwaiters_ready(ctx, S, lv, &wok)) return s;
+        if (ok)
+            if (int s = laspj::lvar_walk_val(ctx, S, lv, threshold, n, &ok)) return s;
+        if (!ok) return laspj::fallback(S);
+        // threshold_met (lasp_lattice.erl:62-75) as laspj_lvar_etf_threshold answers it
+        const laspj::LvOrder ord(ctx, *lv->ns);
+        laspj_buf* res = nullptr;
+        if (int s = laspj_buf_create(ctx, 8, &res)) return s;
+        uint8_t b = 0;
+        int s = laspj_list_inflation(ctx, lv->val, lv->list, strict ? 1 : 0, &ord.o, res);
+        if (s == LASPJ_OK) s = laspj_buf_download(ctx, res, 0, &b, 1);
+        laspj_buf_destroy(res);
+        if (s) return s;
+        ++S->stats[laspj::ST_PASSES];
+        *verdict = LASPJ_NIF_OK;
+        if (b) {
+            *met = 1;
+            return LASPJ_OK;
+        }
+        // unmet (lasp_core.erl:355-364): appended to waiting_threads; the walked threshold
+        // (lv->val) becomes the waiter's list, a fresh block takes its place
+        laspj::LWaiter w;
+        w.id = id;
+        w.strict = strict ? 1 : 0;
+        w.image.assign(threshold, threshold + n);
+        w.n = lv->val->known_e;
+        w.epoch = lv->ns->epoch;
+        lv->waiters.reserve(lv->waiters.size() + 1);
+        laspj_batch* fresh = nullptr;
+        if (int c = laspj_list_batch_create(ctx, LASPJ_KIND_ORSET_LIST, 1, 1, 1, &fresh)) {
+            *verdict = LASPJ_NIF_FALLBACK;
+            return c;
+        }
+        w.list = lv->val;
+        lv->val = fresh;
+        lv->waiters.push_back(std::move(w));
+        return LASPJ_OK;
+    });
+}
+
+int laspj_lvar_recheck(laspj_lvar* lv, uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                       uint32_t* nwaiting, int32_t* verdict) {
+    const laspj::Entry e =
+        enter_lvar(lv, "lvar_recheck", (ids || !cap) && nmet && nwaiting && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    ++S->stats[laspj::ST_CALLS];
+    *nmet = 0;
+    *nwaiting = (uint32_t)lv->waiters.size();
+    *verdict = LASPJ_NIF_FALLBACK;
+    return laspj::nomem_guard(ctx, "lvar_recheck", [&]() -> int {
+        laspj::KindState& K = *lv->ns;
+        bool ok = false;
+        if (int s = laspj::lvar_ready(ctx, S, lv, &ok)) return s;
+        if (ok)
+            if (int s = laspj::lwaiters_ready(ctx, S, lv, &ok)) return s;
+        if (!ok || K.wide || lv->epoch != K.epoch) return laspj::fallback(S);
+        *verdict = LASPJ_NIF_OK;
+        if (lv->waiters.empty()) return LASPJ_OK;
+        if (int s = laspj::lvar_prepare(ctx, S, K)) return s;
+        const std::vector<laspj::ListWaiter> ws = laspj::lwaiter_descs(lv);
+        std::vector<uint8_t> met(ws.size(), 0);
+        const laspj::LvOrder ord(ctx, K);
+        const uint64_t t0 = laspj::now_ns();
+        if (int s = laspj::list_waiters_check(ctx, lv->list, &ord.o, ws.data(),
+                                              (uint32_t)ws.size(), met.data()))
+            return s;
+        ++S->stats[laspj::ST_PASSES];
+        S->stats[laspj::ST_NS_WAIT] += laspj::now_ns() - t0;
+        laspj::lwaiters_take(lv, met.data(), ids, cap, nmet);
+        *nwaiting = (uint32_t)lv->waiters.size();
+        return LASPJ_OK;
+    });
+}
+
+int laspj_lvar_intersection_recheck(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                                    uint64_t* ids, uint32_t cap, uint32_t* nmet,
+                                    uint32_t* nwaiting, int32_t* verdict) {
+    if (!l || !r) return LASPJ_E_INVAL;
+    const laspj::Entry e = enter_lvar(out, "lvar_intersection_recheck",
+                                      status && (ids || !cap) && nmet && nwaiting && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    *status = LASPJ_BIND_NOOP;
+    *verdict = LASPJ_NIF_FALLBACK;
+    *nmet = 0;
+    *nwaiting = (uint32_t)out->waiters.size();
+    if (l->gc || r->gc || l->ctx != ctx || r->ctx != ctx || !S->vars.count(l) || !S->vars.count(r)) {
+        ++S->stats[laspj::ST_CALLS];
+        return laspj::fallback(S);
+    }
+    return laspj::nomem_guard(ctx, "lvar_intersection_recheck", [&]() -> int {
+        // the waiters' thresholds on the device first: what their walk registers joins the
+        // dictionary ahead of the images the producer and the bind run over
+        bool ok = false, wok = false;
+        if (int s = laspj::lvar_ready(ctx, S, out, &ok)) return s;
+        if (ok)
+            if (int s = laspj::lwaiters_ready(ctx, S, out, &wok)) return s;
+        const bool tail = wok && !out->waiters.empty();
+        const std::vector<laspj::ListWaiter> ws =
+            tail ? laspj::lwaiter_descs(out) : std::vector<laspj::ListWaiter>();
+        std::vector<uint8_t> met(ws.size(), 0);
+        if (int s = laspj::lvar_intersection_locked(ctx, S, out, l, r, status, verdict,
+                                                    tail ? &ws : nullptr, met.data()))
+            return s;
+        // NOOP, REFUSED, FALLBACK: the value is as it was, so no registered waiter became met
+        if (*verdict != LASPJ_NIF_OK || *status != LASPJ_BIND_WRITTEN || out->waiters.empty())
+            return LASPJ_OK;
+        if (!tail) {
+            // written, the waiters not checked (an image the walk refuses): the NIF's walk
+            *verdict = LASPJ_NIF_FALLBACK;
+            return laspj::fallback(S);
+        }
+        laspj::lwaiters_take(out, met.data(), ids, cap, nmet);
+        *nwaiting = (uint32_t)out->waiters.size();
+        return LASPJ_OK;
+    });
+}
+
+int laspj_lvar_wait_cancel(laspj_lvar* lv, uint64_t id, int32_t* found) {
+    const laspj::Entry e = enter_lvar(lv, "lvar_wait_cancel", found != nullptr);
+    if (e.rc) return e.rc;
+    *found = 0;
+    std::vector<laspj::LWaiter>& ws = lv->waiters;
+    for (size_t k = 0; k < ws.size(); ++k)
+        if (ws[k].id == id) {
+            laspj::lwaiter_release(ws[k]);
+            ws.erase(ws.begin() + (ptrdiff_t)k);
+            *found = 1;
+            break;
+        }
+    return LASPJ_OK;
+}
+
+int laspj_lvar_waiter_count(const laspj_lvar* lv, uint32_t* n) {
+    laspj::NifState* S = lvar_state(const_cast<laspj_lvar*>(lv));
+    if (!S || !n) return LASPJ_E_INVAL;
+    std::lock_guard<std::mutex> lk(S->mu);
+    *n = (uint32_t)lv->waiters.size();
+    return LASPJ_OK;
+}
+
+int laspj_lvar_waiter_at(laspj_lvar* lv, uint32_t k, uint64_t* id, int32_t* strict,
+                         const uint8_t** threshold, uint64_t* n) {
+    const laspj::Entry e = laspj::enter(lvar_state(lv), lv ? lv->ctx : nullptr, "lvar_waiter_at",
+                                        id && strict && threshold && n);
+    if (e.rc) return e.rc;
+    if (k >= lv->waiters.size())
+        return fail(e.ctx, LASPJ_E_RANGE, "lvar_waiter_at: no waiter %u", k);
+    *id = lv->waiters[k].id;
+    *strict = lv->waiters[k].strict;
+    *threshold = lv->waiters[k].image.data();
+    *n = lv->waiters[k].image.size();
+    return LASPJ_OK;
 }
 
 int laspj_lvar_counts(laspj_lvar* lv, uint32_t* entries, uint32_t* tokens) {

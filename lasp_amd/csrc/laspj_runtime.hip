@@ -295,6 +295,8 @@ int laspj_ctx_destroy(laspj_ctx* ctx) {
         if (ctx->lfz) hipFree(ctx->lfz);
         if (ctx->lfi) hipFree(ctx->lfi);
         if (ctx->lspec) hipFree(ctx->lspec);
+        if (ctx->lw_dev) hipFree(ctx->lw_dev);
+        if (ctx->lw_h) hipHostFree(ctx->lw_h);
         if (ctx->many_h) hipHostFree(ctx->many_h);
         laspj::dev_cache_clear(ctx);
         if (ctx->pinned) hipHostFree(ctx->pinned);

@@ -628,6 +628,60 @@ class NifListVar:
                                               C.byref(res), C.byref(verd)), self.ctx.h)
         return int(verd.value), (bool(res.value) if verd.value == 0 else None)
 
+    def wait(self, img: bytes, strict: bool = False, id: int = 0):
+        """read/6 (laspj_lvar_wait): (verdict, met) — an unmet threshold is registered as a
+        waiter {id, strict, img}; met is None on NIF_FALLBACK."""
+        met, verd = C.c_int32(), C.c_int32()
+        img = bytes(img)
+        check(self.L.laspj_lvar_wait(self.h, img, len(img), int(strict), id, C.byref(met),
+                                     C.byref(verd)), self.ctx.h)
+        return int(verd.value), (bool(met.value) if verd.value == 0 else None)
+
+    def recheck(self, cap: int = 16):
+        """write/4's reply_to_all (laspj_lvar_recheck): (verdict, [ids met, in list order],
+        waiters left); asks again with more room when more than cap are met."""
+        while True:
+            ids = (C.c_uint64 * max(cap, 1))()
+            nmet, left, verd = C.c_uint32(), C.c_uint32(), C.c_int32()
+            check(self.L.laspj_lvar_recheck(self.h, ids, cap, C.byref(nmet), C.byref(left),
+                                            C.byref(verd)), self.ctx.h)
+            if nmet.value <= cap:
+                return int(verd.value), [int(x) for x in ids[:nmet.value]], int(left.value)
+            cap = nmet.value
+
+    def intersection_recheck(self, left: NifVar, right: NifVar, cap: int = 16):
+        """laspj_lvar_intersection_recheck: the intersection's re-run and, when it writes, the
+        waiters' re-check inside the same device pass — (verdict, status, [ids met, in list
+        order], waiters left).  More than cap met: the value is written already, so the ids
+        are fetched by recheck with the room asked for."""
+        ids = (C.c_uint64 * max(cap, 1))()
+        st, nmet, left_n, verd = C.c_int32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        check(self.L.laspj_lvar_intersection_recheck(self.h, left.h, right.h, C.byref(st), ids,
+                                                     cap, C.byref(nmet), C.byref(left_n),
+                                                     C.byref(verd)), self.ctx.h)
+        if nmet.value > cap:
+            verd2, got, n = self.recheck(nmet.value)
+            return verd2, int(st.value), got, n
+        return int(verd.value), int(st.value), [int(x) for x in ids[:nmet.value]], \
+            int(left_n.value)
+
+    def cancel(self, id: int) -> bool:
+        found = C.c_int32()
+        check(self.L.laspj_lvar_wait_cancel(self.h, id, C.byref(found)), self.ctx.h)
+        return bool(found.value)
+
+    def waiters(self):
+        """[(id, strict, threshold image)] in list order."""
+        n = C.c_uint32()
+        check(self.L.laspj_lvar_waiter_count(self.h, C.byref(n)), self.ctx.h)
+        out = []
+        for k in range(n.value):
+            wid, strict, p, ln = C.c_uint64(), C.c_int32(), C.c_void_p(), C.c_uint64()
+            check(self.L.laspj_lvar_waiter_at(self.h, k, C.byref(wid), C.byref(strict),
+                                              C.byref(p), C.byref(ln)), self.ctx.h)
+            out.append((int(wid.value), bool(strict.value), C.string_at(p, ln.value)))
+        return out
+
     def counts(self):
         """(entries, tokens) of the resident list."""
         ne, nt = C.c_uint32(), C.c_uint32()
