@@ -1385,6 +1385,67 @@ int laspj_nif_stats(laspj_ctx* ctx, uint64_t* out, uint32_t n);
  * resident variables are written out to their images and decoded again when used) */
 int laspj_nif_reset(laspj_ctx* ctx);
 
+/* ------------------------------------------------------------------ resident map processes */
+/* lasp_process:process/3 (lasp_process.erl:61-95) re-runs map/6's body (lasp_core.erl:641-667)
+ * whenever its input changes: AccValue = [{F(X), Cx} || {X, Cx} <- Value], bound with bind/3
+ * (:291-312).  F is an Erlang fun only the NIF can call, and pure, so its results are kept
+ * beside the input's namespace: per element slot whether F has been asked (`evaluated`), the
+ * element slot F(X) took (`ymap`) and, per token of X, the slot the token's image holds
+ * under F(X) (`tmap`).  Output terms are registered in the input's namespace exactly as the
+ * walker of an image registers them (laspj_lvar_etf_bind): F(X) as an element, X's tokens as
+ * tokens of that element, so a produced list and a peer's image of the same value agree id
+ * for id, and tokens of two inputs that F sends to one key are ordered in that key's own
+ * rank row.  The NIF's loop: run; while pending > 0: args -> F on each -> results -> run;
+ * after a WRITTEN answer laspj_lvar_recheck(out).  The tables follow the namespace: growth
+ * extends them (bitmaps with zeros, tmap with "unmapped"), a dictionary reset (laspj_nif_reset,
+ * or the 2^20 element cap) releases them, drops an outstanding argument list and forgets a
+ * refusal, so F is asked again; a wide namespace answers FALLBACK. */
+typedef struct laspj_map laspj_map;
+/* One lasp_process running map/6 (lasp_core.erl:641-667) from the resident OR-Set in into the
+ * list-valued variable out of the same context and namespace (out made by laspj_lvar_create
+ * over in or a replica of it).  in not an OR-Set: LASPJ_E_KIND (a list variable holds OR-Set
+ * lists); two namespaces: LASPJ_E_UNSUPPORTED — the NIF keeps the image path, laspj_list_etf_map,
+ * for that process; null arguments: LASPJ_E_INVAL.  Several maps may share one in.
+ * Destroying in, out or the context kills the map: its later calls answer LASPJ_E_INVAL
+ * (laspj_map_destroy still frees it). */
+int laspj_map_create(laspj_var* in, laspj_lvar* out, laspj_map** m);
+/* the process ends (lasp_process.erl:61-95 terminates): its tables are released (the terms it
+ * registered stay in the namespace, as a walked image's do) */
+int laspj_map_destroy(laspj_map* m);
+/* One re-run of map/6's body plus bind/3 (lasp_core.erl:641-667, 291-312).  *pending = the
+ * element slots in holds (any token, tombstoned ones too: the body maps them) that F has not
+ * been asked about.  *pending > 0: out is untouched, *status LASPJ_BIND_NOOP — go through
+ * laspj_map_args / laspj_map_results and run again.  *pending == 0: AccValue has one entry
+ * per held slot, in the term order of the input's keys, its tokens in term order with their
+ * removed flags, and is bound into out as laspj_lvar_intersection binds: *status
+ * LASPJ_BIND_NOOP (`Value0 =:= Value`, :294-296), LASPJ_BIND_WRITTEN, or LASPJ_BIND_REFUSED
+ * (the merge does not inflate out, :301-307: nothing written).  Tokens minted on known
+ * elements since the last run need no fun: the library names them under their keys itself.
+ * One synchronisation in steady state; the waiters of out are not re-checked
+ * (laspj_lvar_recheck after WRITTEN).  verdict FALLBACK, out exactly as it was: in is not a
+ * current resident OR-Set value, the namespace is wide, out is held on the host, or the map
+ * is refused (laspj_map_results). */
+int laspj_map_run(laspj_map* m, int32_t* status, uint32_t* pending, int32_t* verdict);
+/* The arguments map/6's body would call Function on and the device has no result for
+ * (lasp_core.erl:647-660): term_to_binary/1 of their list, one per pending element slot of
+ * the last run, in term order (the order the fold meets them in a canonical value).  Nothing
+ * is registered.  *count may be 0 (the image of []).  *out is valid until the context's
+ * next call; the map remembers the slots it listed.  verdict FALLBACK as laspj_map_run. */
+int laspj_map_args(laspj_map* m, const uint8_t** out, uint64_t* out_len,
+                   uint32_t* count, int32_t* verdict);
+/* Function's results for laspj_map_args' list, in its order (lasp_core.erl:647-660):
+ * term_to_binary/1 of the list of F(X).  Under one dictionary journal each result is
+ * registered as an element of the input's namespace and each token X has registered as a
+ * token of that element.  verdict FALLBACK — the journal rolled back, nothing recorded, the
+ * map refused until the next dictionary reset (its run and args answer FALLBACK; variables
+ * and other maps of the namespace carry on): a result `==` to a registered term under another
+ * image (1 and 1.0 are one orddict key), a result of a term kind the dictionary does not
+ * hold, or an element that would pass 64 tokens (a map never widens its input's namespace).
+ * LASPJ_E_INVAL with nothing recorded: a length other than the list's, or no list
+ * outstanding; after a dictionary reset dropped the list: LASPJ_OK with nothing recorded.
+ * A fun that raised never gets here: the process crashes, as the reference's does. */
+int laspj_map_results(laspj_map* m, const uint8_t* results, uint64_t n, int32_t* verdict);
+
 /* ------------------------------------------------------------------ timing */
 int laspj_event_create(laspj_ctx* ctx, laspj_event** out);
 int laspj_event_destroy(laspj_event* ev);

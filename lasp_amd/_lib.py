@@ -275,6 +275,11 @@ SIGNATURES = {
                                  C.POINTER(u64)]),
     "laspj_lvar_counts": (i, [vp, C.POINTER(u32), C.POINTER(u32)]),
     "laspj_lvar_resident": (i, [vp, C.POINTER(C.c_int32)]),
+    "laspj_map_create": (i, [vp, vp, vpp]),
+    "laspj_map_destroy": (i, [vp]),
+    "laspj_map_run": (i, [vp, C.POINTER(C.c_int32), C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_map_args": (i, [vp, vpp, C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_map_results": (i, [vp, vp, u64, C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,
                                  C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_increment": (i, [vp, vp, u64, vp, u64, vp, u32, C.POINTER(u32),

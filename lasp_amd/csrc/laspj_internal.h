@@ -747,6 +747,30 @@ constexpr uint32_t kLvTile = 1024;      // positions per block: 256 threads x 4
 inline uint32_t lv_isect_tiles(uint32_t n) { return n ? (n + kLvTile - 1) / kLvTile : 1; }
 hipError_t launch_lv_isect(laspj_ctx* ctx, const LvIsect& a, const ListDev& out, uint64_t* tiles,
                            uint32_t* ans);
+// map/6's body (lasp_core.erl:641-667) from one variable's cells and a map process's tables
+// (include/laspj.h "resident map processes"): per term-order position j < n, e =
+// elem_order[j]; a held cell (any token, tombstoned ones too) of an evaluated slot whose
+// present tokens are all mapped emits {ymap[e], its tokens through tmap[e]}, placed by y's
+// rank row.  A held slot F has not seen is pending, a present token with tmap 0xFF unmapped:
+// such a cell emits nothing and the host discards the pass.  The tables cover E slots.
+struct LmMap {
+    const uint64_t* in;
+    uint32_t Ein;
+    uint32_t n;
+    const uint32_t* elem_order;
+    const uint32_t* grank;              // 64 words per element slot
+    const uint64_t* evaluated;          // `words` words
+    uint64_t* pmask;                    // `words` words: the pass's pending slots
+    const uint32_t* ymap;               // E words
+    const uint8_t* tmap;                // 64 E bytes
+    uint32_t E, words;
+};
+// The count launch (tile sums, pmask, rec += {pending, unmapped}: rec two device words the
+// caller keeps zero between passes) and, unless count_only, the writer behind it, whose last
+// tile writes ans = {entries, tokens, overflow, pending, unmapped} (host-visible) and zeroes
+// rec again.  No synchronisation.
+hipError_t launch_lm_map(laspj_ctx* ctx, const LmMap& a, const ListDev& out, uint64_t* tiles,
+                         uint32_t* rec, uint32_t* ans, bool count_only);
 
 // the host's half (laspj_reads_host.cpp: no device, no lock)
 // wave items of a read whose longest block of cells has `words` u64 words

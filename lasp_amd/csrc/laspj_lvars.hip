@@ -20,6 +20,9 @@
 // last tile writes the list's header, the token-offset sentinel and the totals the host
 // reads after the bind's synchronisation.  No block waits on another: the two launches are
 // ordered by the stream.  Every write is checked against the output's capacity.
+//
+// map/6 (lasp_core.erl:641-667; include/laspj.h "resident map processes") is the same producer
+// over one variable's cells and a map process's tables: k_lm_count / k_lm_write below.
 
 #include "laspj_internal.h"
 
@@ -71,8 +74,10 @@ __device__ __forceinline__ Cnt lv_block_excl(Cnt v, Cnt* lds, Cnt* total) {
     return Cnt{before.e + x.e - v.e, before.t + x.t - v.t};
 }
 
-// the element slots of a thread's four positions (kLvNoElem past the last position)
-__device__ __forceinline__ void lv_slots(const LvIsect& a, uint32_t j0, uint32_t* e) {
+// the element slots of a thread's four positions (kLvNoElem past the last position); A: the
+// producer's arguments (elem_order, n)
+template <class A>
+__device__ __forceinline__ void lv_slots(const A& a, uint32_t j0, uint32_t* e) {
     if (j0 + kLvI <= a.n && (reinterpret_cast<uintptr_t>(a.elem_order) & 15u) == 0) {
         const u32x4 v = *reinterpret_cast<const u32x4*>(a.elem_order + j0);
         e[0] = v.x, e[1] = v.y, e[2] = v.z, e[3] = v.w;
@@ -186,6 +191,157 @@ __global__ __launch_bounds__(kLvT) void k_lv_write(LvIsect a, ListDev out, const
     }
 }
 
+// ---- map/6 (lasp_core.erl:641-667) from a variable's cells and a map process's tables ------
+// One entry {F(X), Cx} per held slot e: the key is ymap[e], the element slot F(X) took in the
+// input's namespace, and each token of the cell is named by the slot its image holds under
+// that element (tmap[e][k]), so every run is ordered inside one rank row, y's — also where
+// F sends two inputs to one key.
+
+// what slot e's cell gives: its entry's counts, the key, the present and removed masks in
+// the key's slot space; un: present tokens without a mapping (the cell then emits nothing,
+// as does a held slot F has not been asked about: the slot-order half counts that one)
+struct LmCell {
+    Cnt c;
+    uint32_t y, un;
+    u64 q, qr;
+};
+
+__device__ __forceinline__ LmCell lm_cell(const LmMap& a, uint32_t e) {
+    LmCell o{Cnt{0, 0}, 0, 0, 0, 0};
+    if (e >= a.Ein || e >= a.E) return o;
+    const u64x2 C = *reinterpret_cast<const u64x2*>(a.in + 2ull * e);
+    if (!C.x || !((a.evaluated[e >> 6] >> (e & 63u)) & 1ull)) return o;
+    o.y = a.ymap[e];
+    const uint8_t* tm = a.tmap + 64ull * e;
+    if (o.y >= a.E) {                                      // (no table row: nothing to place by)
+        o.un = (uint32_t)__popcll(C.x);
+        return o;
+    }
+    if ((C.x & (C.x - 1)) == 0) {                          // one token: one byte
+        const uint32_t k = (uint32_t)__builtin_ctzll(C.x), k2 = tm[k];
+        if (k2 >= 64u) {
+            o.un = 1;
+            return o;
+        }
+        o.q = 1ull << k2;
+        o.qr = ((C.y >> k) & 1ull) << k2;
+    } else {
+        for (u64 b = C.x; b; b &= b - 1) {
+            const uint32_t k = (uint32_t)__builtin_ctzll(b), k2 = tm[k];
+            if (k2 >= 64u) {
+                ++o.un;
+                continue;
+            }
+            o.q |= 1ull << k2;
+            o.qr |= ((C.y >> k) & 1ull) << k2;
+        }
+        if (o.un) return o;
+    }
+    o.c = Cnt{1u, (uint32_t)__popcll(o.q)};
+    return o;
+}
+
+__device__ __forceinline__ void lm_rec_add(uint32_t* p, uint32_t v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kLvT) void k_lm_count(LmMap a, u64* tiles, uint32_t* rec) {
+    __shared__ Cnt lds[kLvT / 64];
+    const uint32_t lane = threadIdx.x & 63u;
+    // the filter's check over this tile's element slots in slot order: a wave's 64 slots are
+    // one word of the bitmaps, four words per wave
+    {
+        const uint32_t w0 = (blockIdx.x * kLvTile + (threadIdx.x & ~63u) * kLvI) >> 6;
+        uint32_t pend = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kLvI; ++i) {
+            const uint32_t w = w0 + i, s = 64u * w + lane;
+            if (w >= a.words) break;                       // (wave-uniform)
+            const bool held = s < a.Ein && a.in[2ull * s] != 0;
+            const u64 pm = __ballot(held) & ~a.evaluated[w];
+            if (lane == 0) a.pmask[w] = pm;
+            pend += (uint32_t)__popcll(pm);
+        }
+        if (lane == 0 && pend) lm_rec_add(rec, pend);
+    }
+    const uint32_t j0 = blockIdx.x * kLvTile + threadIdx.x * kLvI;
+    uint32_t e[kLvI];
+    lv_slots(a, j0, e);
+    Cnt mine{0, 0};
+    uint32_t un = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        const LmCell c = lm_cell(a, e[k]);
+        mine.e += c.c.e;
+        mine.t += c.c.t;
+        un += c.un;
+    }
+    if (__ballot(un != 0)) {                               // (rare: a token minted since)
+        for (int s = 32; s; s >>= 1) un += __shfl_xor(un, s, 64);
+        if (lane == 0) lm_rec_add(rec + 1, un);
+    }
+    Cnt tot;
+    lv_block_excl(mine, lds, &tot);
+    if (threadIdx.x == 0) {
+        tiles[2ull * blockIdx.x] = tot.e;
+        tiles[2ull * blockIdx.x + 1] = tot.t;
+    }
+}
+
+__global__ __launch_bounds__(kLvT) void k_lm_write(LmMap a, ListDev out, const u64* tiles,
+                                                   uint32_t* rec, uint32_t* ans) {
+    __shared__ Cnt lds[kLvT / 64];
+    Cnt pre{0, 0};
+    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += kLvT) {
+        pre.e += (uint32_t)tiles[2ull * i];
+        pre.t += (uint32_t)tiles[2ull * i + 1];
+    }
+    Cnt base;
+    lv_block_excl(pre, lds, &base);
+    const uint32_t j0 = blockIdx.x * kLvTile + threadIdx.x * kLvI;
+    uint32_t e[kLvI];
+    lv_slots(a, j0, e);
+    LmCell c[kLvI];
+    Cnt mine{0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        c[k] = lm_cell(a, e[k]);
+        mine.e += c[k].c.e;
+        mine.t += c[k].c.t;
+    }
+    Cnt tot;
+    const Cnt ex = lv_block_excl(mine, lds, &tot);
+    uint32_t pos = base.e + ex.e, tp = base.t + ex.t;
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        if (!c[k].c.e) continue;
+        if (pos < out.ce && (u64)tp + c[k].c.t <= out.ct) {
+            out.key[pos] = c[k].y;
+            out.toff[pos] = tp;
+            // the run in y's slot space, placed by the popcount of lower ranks in y's row
+            lv_run(out.tok + tp, c[k].y, c[k].q, c[k].qr, a.grank + 64ull * c[k].y);
+        }
+        pos += 1;
+        tp += c[k].c.t;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        const uint32_t ne = base.e + tot.e, nt = base.t + tot.t;
+        const bool over = ne > out.ce || nt > out.ct;
+        out.hdr[0] = over ? 0u : ne;
+        out.hdr[1] = over ? 0u : nt;
+        out.toff[over ? 0u : ne] = over ? 0u : nt;
+        ans[0] = ne;
+        ans[1] = nt;
+        ans[2] = over ? 1u : 0u;
+        // the count launch's {pending, unmapped} (the stream put it ahead of this one), and
+        // the words zero again for the next pass
+        ans[3] = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ans[4] = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rec[0] = 0;
+        rec[1] = 0;
+    }
+}
+
 // one wave per element slot: lane j reads the slot of term-order place j of its tokens
 __global__ __launch_bounds__(256) void k_lv_ranks(const uint32_t* __restrict__ elem_order,
                                                   const uint8_t* __restrict__ tok_order, uint32_t E,
@@ -223,6 +379,16 @@ hipError_t launch_lv_isect(laspj_ctx* ctx, const LvIsect& a, const ListDev& out,
     const uint32_t ntile = lv_isect_tiles(a.n);
     hipLaunchKernelGGL(k_lv_count, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, tiles);
     hipLaunchKernelGGL(k_lv_write, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, out, tiles, ans);
+    return hipGetLastError();
+}
+
+hipError_t launch_lm_map(laspj_ctx* ctx, const LmMap& a, const ListDev& out, uint64_t* tiles,
+                         uint32_t* rec, uint32_t* ans, bool count_only) {
+    const uint32_t ntile = lv_isect_tiles(a.n);
+    hipLaunchKernelGGL(k_lm_count, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, tiles, rec);
+    if (!count_only)
+        hipLaunchKernelGGL(k_lm_write, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, out, tiles, rec,
+                           ans);
     return hipGetLastError();
 }
 

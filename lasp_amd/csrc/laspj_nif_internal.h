@@ -1,5 +1,5 @@
 // What the NIF-level translation units share (laspj_nif.hip and laspj_nif_{vars,waiters,
-// process,lvars}.hip): the per-context state, a call's description, the functions one file
+// process,lvars,maps}.hip): the per-context state, a call's description, the functions one file
 // defines and another calls (each with the lock its caller holds), and the opening, the
 // allocation guard and the FALLBACK ending the entry points have in common.
 #pragma once
@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "laspj_internal.h"
+
+struct laspj_map;
 
 namespace laspj {
 
@@ -67,6 +69,10 @@ struct KindState {
     bool rank_full = true;
     std::vector<uint32_t> rank_dirty;
     uint64_t built_toks = 0;        // the tokens `etf` holds over all elements (sum of built_cnt)
+    // the map processes over this dictionary (laspj_map): patch_etf hands each the slots it
+    // rewrote — elements that gained tokens, which the map then names under its keys before
+    // its next pass — and rebuild_etf says "all"
+    std::unordered_set<laspj_map*> maps;
 };
 
 // One entry of `#dv.waiting_threads` ({threshold, read, From, Type, Threshold},
@@ -164,6 +170,47 @@ struct laspj_lvar {
     laspj_batch* tmp = nullptr;      // l's list form (the two-step composition, A/B only)
     std::vector<uint8_t> image;
     std::vector<laspj::LWaiter> waiters;   // `#dv.waiting_threads`, in list order
+};
+
+// One lasp_process running map/6 (lasp_core.erl:641-667) from the OR-Set `in` into the list
+// variable `out` (include/laspj.h "resident map processes").  Per element slot e of the
+// namespace: whether F has been asked (evaluated), the element slot F(X) took (ymap) and, per
+// token slot k of e, the slot the token's image holds under ymap[e] (tmap, 0xFF: not mapped).
+// On the device (dev: [rec {pending, unmapped} | evaluated | pmask | ymap | tmap], over E
+// slots) with all but pmask mirrored on the host, where laspj_map_results and the token
+// fan-out edit them; rows that changed are uploaded ahead of the next pass.
+struct laspj_map {
+    laspj_ctx* ctx = nullptr;        // null once the context is gone
+    laspj_var* in = nullptr;         // null once in or out is destroyed: the map is dead
+    laspj_lvar* out = nullptr;       // and its calls answer LASPJ_E_INVAL
+    std::shared_ptr<laspj::KindState> ns;
+    uint64_t epoch = 0;              // the dictionary generation the tables refer to
+    uint32_t E = 0, words = 0;       // the slots the device tables cover
+    uint8_t* dev = nullptr;
+    uint64_t dev_bytes = 0;
+    std::vector<uint64_t> h_eval;
+    std::vector<uint32_t> h_ymap;
+    std::vector<uint8_t> h_tmap;     // 64 per slot
+    // per slot: the token slots this map's own registrations created under it (the images
+    // of some input's tokens: never tokens of that element in `in`, so not mapped onwards),
+    // and how many of its tokens have been looked at
+    std::vector<uint64_t> h_mine;
+    std::vector<uint8_t> h_seen;
+    // mirror rows the device has not got yet: the slots whose evaluated bit / ymap changed
+    // (as a range) and the slots whose tmap row changed
+    uint32_t up_lo = ~0u, up_hi = 0;
+    std::vector<uint32_t> up_rows;
+    bool pmask_valid = false;        // pmask is a pass's of this generation and size
+    bool rec_dirty = true;           // rec is not known zero (a pass without its writer)
+    bool refused = false;            // until the next dictionary reset: FALLBACK
+    bool val_not_asc = false;        // the produced list's keys do not ascend (F's order)
+    // the element slots whose tokens grew since the last look (patch_etf), or all of them
+    std::vector<uint32_t> tok_dirty;
+    bool tok_all = true;
+    // laspj_map_args' list, as the filter's
+    std::vector<uint32_t> listed;
+    bool outstanding = false, dropped = false;
+    std::string image;
 };
 
 namespace laspj {
@@ -279,6 +326,7 @@ struct NifState {
     uint64_t lv_tiles_bytes = 0;
     uint32_t* lv_ans = nullptr;
     uint32_t* lv_ans_d = nullptr;
+    std::unordered_set<laspj_map*> maps;         // the live map processes
 };
 
 enum class Op { MERGE, VALUE, EQUAL, INFLATION, BIND, WRITE, THRESHOLD, READ, VVALUE };
@@ -429,6 +477,59 @@ void waiter_cells_drop(NifState* S, laspj_var* c);
 int spill_lvars(NifState* S, KindState& K);
 // a list variable's waiter gives its device list back, its image stays (the context alive)
 void lwaiter_release(LWaiter& w);
+// what a call registered in the namespace since `before`: the device images are stale
+struct RegMark {
+    uint32_t n = 0;
+    uint64_t tb = 0;
+};
+RegMark reg_mark(const KindState& K);
+void reg_note(NifState* S, KindState& K, const RegMark& before);
+// the namespace's device images brought up to its dictionary (S->mu held, ctx->mu not; at
+// least one element registered); the order tables derived from them, fully or for the
+// patched slots (ctx->mu held)
+int lvar_images(laspj_ctx* ctx, NifState* S, KindState& K);
+int lvar_ranks(laspj_ctx* ctx, NifState* S, KindState& K);
+// the tables as the list entry points take them (the bufs are views, never destroyed)
+struct LvOrder {
+    laspj_buf kb, gb;
+    laspj_list_order o{};
+    LvOrder(laspj_ctx* ctx, const KindState& K) {
+        kb.ctx = gb.ctx = ctx;
+        kb.dev = K.krank;
+        kb.bytes = K.krank_bytes;
+        gb.dev = K.grank;
+        gb.bytes = K.grank_bytes;
+        o.krank = &kb;
+        o.nkeys = K.rank_E;
+        o.grank = &gb;
+        o.ntokens = 64u * K.rank_E;
+    }
+};
+// *ok: the variable's list is on the device over the current dictionary (S->mu held)
+int lvar_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok);
+// the producers' scratch: tile sums (S->lv_tiles) and pinned totals (S->lv_ans); ctx->mu held
+int lvar_scratch(laspj_ctx* ctx, NifState* S, uint32_t ntile);
+
+// ---- laspj_nif_process.hip --------------------------------------------------------------
+// a small upload through the staging ring (larger ones straight from `src`), enqueued
+hipError_t proc_upload(laspj_ctx* ctx, void* dst, const void* src, uint64_t bytes);
+// the elements of a proper list image (131 + the list); a STRING_EXT's bytes stand as empty
+// views, or — bytes given — as SMALL_INTEGER_EXT images built there
+bool image_list(const uint8_t* p, uint64_t n, std::vector<std::string_view>* out,
+                std::string* bytes = nullptr);
+// laspj_filter_args' list for a process over K: the slots of pm (a check pass's pending
+// words) without a result in h_eval, in term order (*slots), and the image of their
+// arguments' list (pair_first: a 2-tuple element gives its first component)
+void proc_args_image(const KindState& K, const std::vector<uint64_t>& pm,
+                     const std::vector<uint64_t>& h_eval, bool pair_first,
+                     std::vector<uint32_t>* slots, std::string* image);
+
+// ---- laspj_nif_maps.hip -----------------------------------------------------------------
+// a variable / a list variable / the context goes: the maps naming it are dead from here on
+// (S->mu and ctx->mu held)
+void maps_var_gone(NifState* S, laspj_var* v);
+void maps_lvar_gone(NifState* S, laspj_lvar* lv);
+void maps_ctx_gone(laspj_ctx* ctx, NifState* S);
 
 // ---- what the entry points open and close with ------------------------------------------
 // An entry point's opening: the handle's context state, the null-argument check, the call

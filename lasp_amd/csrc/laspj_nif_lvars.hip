@@ -56,11 +56,10 @@ int lvar_spill(NifState* S, laspj_lvar* lv) {
     return LASPJ_OK;
 }
 
+}  // namespace
+
+// (reg_mark to lvar_ready, and lvar_scratch: shared with the map processes, laspj_nif_maps.hip)
 // what a walk registered in the namespace: the device images are stale from here on
-struct RegMark {
-    uint32_t n = 0;
-    uint64_t tb = 0;
-};
 RegMark reg_mark(const KindState& K) {
     RegMark m;
     uint64_t eb = 0;
@@ -129,23 +128,6 @@ int lvar_ranks(laspj_ctx* ctx, NifState* S, KindState& K) {
     return LASPJ_OK;
 }
 
-// the tables as the list entry points take them (the bufs are views, never destroyed)
-struct LvOrder {
-    laspj_buf kb, gb;
-    laspj_list_order o{};
-    LvOrder(laspj_ctx* ctx, const KindState& K) {
-        kb.ctx = gb.ctx = ctx;
-        kb.dev = K.krank;
-        kb.bytes = K.krank_bytes;
-        gb.dev = K.grank;
-        gb.bytes = K.grank_bytes;
-        o.krank = &kb;
-        o.nkeys = K.rank_E;
-        o.grank = &gb;
-        o.ntokens = 64u * K.rank_E;
-    }
-};
-
 // *ok: the variable's list is on the device over the current dictionary.  A list written
 // out by a dictionary reset is walked back in here (its terms registered afresh); in a wide
 // namespace, or when the walk refuses the image, it stays host-held.  S->mu held.
@@ -175,6 +157,8 @@ int lvar_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
     return LASPJ_OK;
 }
 
+namespace {
+
 // images and tables ready for a list kernel over the namespace (S->mu held, ctx->mu not)
 int lvar_prepare(laspj_ctx* ctx, NifState* S, KindState& K) {
     if (K.dict && dict_elements(K.dict) > 0)
@@ -203,6 +187,8 @@ int lvar_bind(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, int32_t* status,
     return LASPJ_OK;
 }
 
+}  // namespace
+
 // the producer's scratch: tile sums on the device, its totals in pinned memory (ctx->mu held)
 int lvar_scratch(laspj_ctx* ctx, NifState* S, uint32_t ntile) {
     if (int s = grow_dev(ctx, &S->lv_tiles, &S->lv_tiles_bytes, 16ull * ntile)) return s;
@@ -222,6 +208,8 @@ int lvar_scratch(laspj_ctx* ctx, NifState* S, uint32_t ntile) {
     S->lv_ans_d = static_cast<uint32_t*>(d);
     return LASPJ_OK;
 }
+
+namespace {
 
 // laspj_lvar_intersection with S->mu held and the handles checked
 int lvar_intersection_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj_var* l,
@@ -492,6 +480,7 @@ int laspj_lvar_destroy(laspj_lvar* lv) {
         if (lv->ctx) {
             S->lvars.erase(lv);
             lv->ns->lvars.erase(lv);
+            laspj::maps_lvar_gone(S, lv);        // a map writing into it is dead from here on
             lvar_free_batches(lv);
             // the namespace's last holder: its dictionary, device images and tables go too
             if (lv->ns.use_count() == 1) laspj::free_ns(*lv->ns);

@@ -44,16 +44,26 @@ bool image_is_true(std::string_view v) {
     return false;
 }
 
-// the elements of a proper list image (131 + the list); a STRING_EXT's bytes stand as empty
-// views (small integers: none is `true`)
-bool image_list(const uint8_t* p, uint64_t n, std::vector<std::string_view>* out) {
+}  // namespace
+
+bool laspj::image_list(const uint8_t* p, uint64_t n, std::vector<std::string_view>* out,
+                       std::string* bytes) {
     out->clear();
     if (!p || n < 2 || p[0] != 131 || laspj::list_term_len(p + 1, n - 1) != n - 1) return false;
     const uint8_t* t = p + 1;
     const size_t tn = n - 1;
     if (t[0] == 106) return true;
     if (t[0] == 107) {
-        out->assign(((size_t)t[1] << 8) | t[2], std::string_view());
+        const size_t cnt = ((size_t)t[1] << 8) | t[2];
+        out->assign(cnt, std::string_view());
+        if (bytes) {
+            bytes->resize(2 * cnt);
+            for (size_t i = 0; i < cnt; ++i) {
+                (*bytes)[2 * i] = (char)97;
+                (*bytes)[2 * i + 1] = (char)t[3 + i];
+                (*out)[i] = std::string_view(bytes->data() + 2 * i, 2);
+            }
+        }
         return true;
     }
     if (t[0] != 108) return false;
@@ -67,6 +77,10 @@ bool image_list(const uint8_t* p, uint64_t n, std::vector<std::string_view>* out
     }
     return off < tn && t[off] == 106;
 }
+
+namespace {
+
+using laspj::image_list;
 
 // term images -> 131 + the list as term_to_binary/1 writes it (STRING_EXT for a list of
 // integers 0..255, NIL_EXT when empty)
@@ -92,11 +106,48 @@ void image_write_list(const std::vector<std::string_view>& items, std::string* o
     o->push_back((char)106);
 }
 
-hipError_t proc_upload(laspj_ctx* ctx, void* dst, const void* src, uint64_t bytes) {
+}  // namespace
+
+hipError_t laspj::proc_upload(laspj_ctx* ctx, void* dst, const void* src, uint64_t bytes) {
     if (!bytes) return hipSuccess;
     const void* staged = laspj::stage_small(ctx, src, bytes);
     return hipMemcpyAsync(dst, staged ? staged : src, bytes, hipMemcpyHostToDevice, ctx->stream);
 }
+
+void laspj::proc_args_image(const KindState& K, const std::vector<uint64_t>& pm,
+                            const std::vector<uint64_t>& h_eval, bool pair_first,
+                            std::vector<uint32_t>* slots, std::string* image) {
+    // the pending slots (results recorded since the pass taken off) in term order: the
+    // order the body calls F in over a canonical value
+    slots->clear();
+    const uint32_t known = K.dict ? laspj::dict_elements(K.dict) : 0;
+    for (uint32_t w = 0; w < pm.size(); ++w)
+        for (uint64_t m = pm[w] & ~(w < h_eval.size() ? h_eval[w] : 0ull); m; m &= m - 1) {
+            const uint32_t e = 64u * w + (uint32_t)__builtin_ctzll(m);
+            if (e < known) slots->push_back(e);
+        }
+    auto img = [&](uint32_t e) { return laspj::list_elem_image(K.dict, e); };
+    std::sort(slots->begin(), slots->end(), [&](uint32_t a, uint32_t b) {
+        const std::string_view x = img(a), y = img(b);
+        int c = 0;
+        laspj_term_compare(reinterpret_cast<const uint8_t*>(x.data()), x.size(),
+                           reinterpret_cast<const uint8_t*>(y.data()), y.size(), &c);
+        return c < 0;
+    });
+    // F's argument: the element; a G-Set 2-tuple element's first component
+    std::vector<std::string_view> items;
+    items.reserve(slots->size());
+    for (uint32_t e : *slots) {
+        const std::string_view x = img(e);
+        const size_t l0 = pair_first ? first_of_pair(x) : 0;
+        items.push_back(l0 ? x.substr(2, l0) : x);
+    }
+    image_write_list(items, image);
+}
+
+namespace {
+
+using laspj::proc_upload;
 
 // the filter's context state; null: the context is gone
 NifState* filter_state(laspj_filter* f) {
@@ -343,33 +394,8 @@ int filter_args_locked(laspj_ctx* ctx, NifState* S, laspj_filter* f, const uint8
         pm.resize(f->words);
         LJ_HIP(ctx, laspj::readback(ctx, pm.data(), f->dev + 2ull * f->words, 8ull * f->words));
     }
-    // the pending slots (results recorded since the pass taken off) in term order: the
-    // order the body calls F in over a canonical value
     std::vector<uint32_t> slots;
-    const uint32_t known = K.dict ? laspj::dict_elements(K.dict) : 0;
-    for (uint32_t w = 0; w < pm.size(); ++w)
-        for (uint64_t m = pm[w] & ~f->h_eval[w]; m; m &= m - 1) {
-            const uint32_t e = 64u * w + (uint32_t)__builtin_ctzll(m);
-            if (e < known) slots.push_back(e);
-        }
-    auto img = [&](uint32_t e) { return laspj::list_elem_image(K.dict, e); };
-    std::sort(slots.begin(), slots.end(), [&](uint32_t a, uint32_t b) {
-        const std::string_view x = img(a), y = img(b);
-        int c = 0;
-        laspj_term_compare(reinterpret_cast<const uint8_t*>(x.data()), x.size(),
-                           reinterpret_cast<const uint8_t*>(y.data()), y.size(), &c);
-        return c < 0;
-    });
-    // F's argument: the element; a G-Set 2-tuple element's first component
-    std::vector<std::string_view> items;
-    items.reserve(slots.size());
-    const bool gset = f->in->kind == LASPJ_KIND_GSET;
-    for (uint32_t e : slots) {
-        const std::string_view x = img(e);
-        const size_t l0 = gset ? first_of_pair(x) : 0;
-        items.push_back(l0 ? x.substr(2, l0) : x);
-    }
-    image_write_list(items, &f->image);
+    laspj::proc_args_image(K, pm, f->h_eval, f->in->kind == LASPJ_KIND_GSET, &slots, &f->image);
     f->listed.swap(slots);
     f->outstanding = true;
     f->dropped = false;

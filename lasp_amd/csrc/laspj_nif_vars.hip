@@ -554,6 +554,7 @@ int laspj_var_destroy(laspj_var* v) {
                         f->in = f->out = nullptr;
                         f->ns.reset();
                     }
+                laspj::maps_var_gone(S, v);              // a map reading it, likewise
             }
             // the namespace's last variable: its device images go too
             if (v->ns.use_count() == 1) laspj::free_ns(*v->ns);
