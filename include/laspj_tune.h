@@ -16,8 +16,9 @@ extern "C" {
                                         kernels (reduce segments, fragment, value, stats,
                                         equal, inflation, G-Counter sums / threshold /
                                         inflation / increment, filter, fused gather +
-                                        inflation), so tests reach their strides with few
-                                        items; 0 = each launch's own default            */
+                                        inflation, OR-Set from_binary segment decoders),
+                                        so tests reach their strides with few items;
+                                        0 = each launch's own default                   */
 #define LASPJ_TUNE_STREAM_UNROLL 2   /* 16-B cells per lane per iteration: 1,2,4,8      */
 #define LASPJ_TUNE_STREAM_NT     3   /* 1 = non-temporal loads/stores, 0 = default      */
 #define LASPJ_TUNE_ETF_KERNEL    4   /* OR-Set payload writer: 0 = record kernel when the
@@ -85,6 +86,14 @@ extern "C" {
                                         3 = the chunked walk whenever few replicas merge;
                                         2 = list_bind never takes its rank-indexed path
                                         (both lists ascending); for A/B               */
+#define LASPJ_TUNE_ETF_OCC      11   /* OR-Set from_binary segment decoders: 0 = chosen
+                                        by the launch (the under-filled form — one wave
+                                        per workgroup, bounds loose enough that no
+                                        register spills — up to the 48 waves per CU
+                                        that segments are sized for, else the filled
+                                        form: 256 threads at 6 waves per SIMD), 1 =
+                                        always the filled form, 2 = always the
+                                        under-filled form                              */
 #define LASPJ_TUNE_NIF_PASSES   14   /* NIF entry points: device passes a call may take
                                         (0 = default 6; registering unseen terms, a grown
                                         answer area and a serial re-decode take one each).

@@ -40,6 +40,7 @@ TUNE_PRODUCT_COLS = 7
 TUNE_ETF_READ = 8
 TUNE_ETF_SEG = 9
 TUNE_LIST_WALK = 10
+TUNE_ETF_OCC = 11
 TUNE_NIF_PASSES = 14
 TUNE_LIST_CHUNK = 15
 TUNE_LVAR_PRODUCER = 16

@@ -3627,18 +3627,35 @@ __device__ __forceinline__ uint64_t seg_replica(const uint32_t* segbase, uint64_
     return lo;
 }
 
-template <bool SMALL>
-__global__ __launch_bounds__(kBlock, 6) void k_orset_etf_read_seg(
+// The segment decoders come in two forms (LASPJ_TUNE_ETF_OCC; DESIGN.md §4 "Under-filled
+// segment launches").  Filled: kBlock threads at 6 waves per SIMD — 80 VGPRs, for launches
+// with more waves than the chip holds.  Under-filled: one wave per workgroup (a single long
+// payload's few hundred waves then spread over as many CUs) at 2 waves per SIMD, under
+// which none of the instantiations spills a register: a launch that cannot fill the chip
+// gains nothing from the occupancy the filled form pays its scratch frame for.
+constexpr int kSegUnderBlock = 64;       // threads per workgroup, under-filled form
+constexpr int kSegUnderWaves = 2;        // waves per SIMD its bounds ask for
+template <bool UNDER>
+struct SegForm {
+    static constexpr int block = UNDER ? kSegUnderBlock : kBlock;
+    static constexpr int waves = block / 64;                          // per workgroup
+    static constexpr int per_simd = UNDER ? kSegUnderWaves : 6;       // launch bounds
+};
+
+template <bool SMALL, bool UNDER>
+__global__ __launch_bounds__(SegForm<UNDER>::block, SegForm<UNDER>::per_simd)
+void k_orset_etf_read_seg(
     const uint8_t* payload, u64 total, const u64* offs, uint64_t R, uint32_t E, DictView d,
     ReadTabs tabs, int tag, int vers, u64x2* cells, const uint32_t* segbase, uint64_t nseg,
     uint32_t S, HdrHash hh, SegRes* res, SegList only) {
-    __shared__ __attribute__((aligned(16))) ReadLds lds[kBlock / 64];
+    constexpr int kWaves = SegForm<UNDER>::waves;
+    __shared__ __attribute__((aligned(16))) ReadLds lds[kWaves];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
     const Cases cs = lane_cases(lane);
     ReadLds& L = lds[wave];
     const uint64_t count = only.n ? only.n : nseg;
-    for (uint64_t j = (uint64_t)blockIdx.x * (kBlock / 64) + wave; j < count; j += nwaves) {
+    for (uint64_t j = (uint64_t)blockIdx.x * kWaves + wave; j < count; j += nwaves) {
         const uint64_t g = only.n ? only.g[j] : j;
         const uint64_t rep = seg_replica(segbase, R, g);
         const uint32_t s = (uint32_t)(g - ufl32(segbase[rep]));
@@ -3706,18 +3723,20 @@ struct DecTabs {
     uint32_t small;      // d.tok_max <= kSmallTok
 };
 
-template <bool SMALL>
-__global__ __launch_bounds__(kBlock, 6) void k_orset_etf_read_seg_multi(
+template <bool SMALL, bool UNDER>
+__global__ __launch_bounds__(SegForm<UNDER>::block, SegForm<UNDER>::per_simd)
+void k_orset_etf_read_seg_multi(
     const uint8_t* payload, u64 total, const u64* offs, uint64_t R, const DecTabs* dts,
     const uint32_t* pay_dt, int tag, int vers, const uint32_t* segbase, uint64_t nseg,
     uint32_t S, SegRes* res, SegList only) {
-    __shared__ __attribute__((aligned(16))) ReadLds lds[kBlock / 64];
+    constexpr int kWaves = SegForm<UNDER>::waves;
+    __shared__ __attribute__((aligned(16))) ReadLds lds[kWaves];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
     const Cases cs = lane_cases(lane);
     ReadLds& L = lds[wave];
     const uint64_t count = only.n ? only.n : nseg;
-    for (uint64_t j = (uint64_t)blockIdx.x * (kBlock / 64) + wave; j < count; j += nwaves) {
+    for (uint64_t j = (uint64_t)blockIdx.x * kWaves + wave; j < count; j += nwaves) {
         const uint64_t g = only.n ? only.g[j] : j;
         const uint64_t rep = seg_replica(segbase, R, g);
         const uint32_t k = ufl32(pay_dt[rep]);
@@ -4979,6 +4998,30 @@ void etf_read_plan(const laspj_ctx* ctx, const laspj_etf_dict* d, uint64_t R, co
     plan->nseg = acc;
 }
 
+// The form and grid of a segment-decoder launch of `waves` segments (one wave each): the
+// under-filled form up to the cus * 48 waves etf_read_plan sizes segments for.  Below
+// cus * 4 SIMDs * kSegUnderWaves the chip holds the whole launch resident at that form's
+// bounds; from there to cus * 48 it was measured faster or level at every size tried
+// (bind_many of 8 .. 64 long payloads, 1.9k .. 12k waves; DESIGN.md §4 "Under-filled
+// segment launches").  Launches larger still (many payloads of a segment or two each) were
+// not measured and keep the filled form.  LASPJ_TUNE_ETF_OCC forces either.  Both stride
+// over the segments past cus * 256 waves, or past LASPJ_TUNE_STREAM_GRID workgroups.
+struct SegShape {
+    bool under;
+    unsigned grid, block;
+};
+
+static SegShape seg_shape(const laspj_ctx* ctx, uint64_t waves) {
+    const bool under = ctx->tune_etf_occ ? ctx->tune_etf_occ == 2
+                                         : waves <= (uint64_t)ctx->cus * 48;
+    const uint64_t per = under ? SegForm<true>::waves : SegForm<false>::waves;
+    const uint64_t blocks = std::max<uint64_t>(1, (waves + per - 1) / per);
+    const uint64_t cap = ctx->tune_grid > 0 ? (uint64_t)ctx->tune_grid
+                                            : (uint64_t)ctx->cus * 256 / per;
+    return {under, (unsigned)std::min(blocks, cap),
+            (unsigned)(under ? SegForm<true>::block : SegForm<false>::block)};
+}
+
 int etf_read_enqueue(laspj_ctx* ctx, laspj_batch* b, const laspj_etf_dict* d, int tag, int vers,
                      const uint8_t* payload, uint64_t payload_bytes, const u64* offs,
                      const EtfReadPlan& plan, const uint32_t* segbase, int32_t* status,
@@ -5019,10 +5062,13 @@ int etf_read_enqueue(laspj_ctx* ctx, laspj_batch* b, const laspj_etf_dict* d, in
         const bool deferred = defer && defer->res;
         SegRes* dres = deferred ? static_cast<SegRes*>(defer->res)
                                 : reinterpret_cast<SegRes*>(sc + o_res);
-        const uint64_t sblocks = (nseg + 3) / 4, scap = (uint64_t)ctx->cus * 64;
+        const SegShape sh = seg_shape(ctx, only && only->n ? only->n : nseg);
         const bool small = small_dict(d) && form != 2;
-        hipLaunchKernelGGL(small ? k_orset_etf_read_seg<true> : k_orset_etf_read_seg<false>,
-                           dim3((unsigned)std::min(sblocks, scap)), dim3(kBlock), 0, ctx->stream,
+        hipLaunchKernelGGL(sh.under ? (small ? k_orset_etf_read_seg<true, true>
+                                             : k_orset_etf_read_seg<false, true>)
+                                    : (small ? k_orset_etf_read_seg<true, false>
+                                             : k_orset_etf_read_seg<false, false>),
+                           dim3(sh.grid), dim3(sh.block), 0, ctx->stream,
                            payload, (u64)payload_bytes, offs, R, b->elements, view(d), tabs, tag,
                            vers, reinterpret_cast<u64x2*>(b->dev), dsegbase, nseg,
                            (uint32_t)plan.S, hh, dres, only ? *only : SegList{});
@@ -5136,11 +5182,14 @@ int etf_read_multi_enqueue(laspj_ctx* ctx, const EtfGroup* g, uint32_t ngroups,
             if (int s2 = reserve_scratch(ctx, sizeof(SegRes) * nseg)) return s2;
             dres = static_cast<SegRes*>(ctx->scratch);
         }
-        const uint64_t sblocks = (nseg + 3) / 4, scap = (uint64_t)ctx->cus * 64;
+        const SegShape sh = seg_shape(ctx, only && only->n ? only->n : nseg);
         for (int sm = 1; sm >= 0; --sm) {
             if (!any[sm]) continue;
-            hipLaunchKernelGGL(sm ? k_orset_etf_read_seg_multi<true> : k_orset_etf_read_seg_multi<false>,
-                               dim3((unsigned)std::min(sblocks, scap)), dim3(kBlock), 0, ctx->stream,
+            hipLaunchKernelGGL(sh.under ? (sm ? k_orset_etf_read_seg_multi<true, true>
+                                              : k_orset_etf_read_seg_multi<false, true>)
+                                        : (sm ? k_orset_etf_read_seg_multi<true, false>
+                                              : k_orset_etf_read_seg_multi<false, false>),
+                               dim3(sh.grid), dim3(sh.block), 0, ctx->stream,
                                payload, (u64)payload_bytes, offs, R, dts, pd, -1, 1, segbase, nseg,
                                (uint32_t)plan.S, dres, only ? *only : SegList{});
             LJ_LAUNCHED(ctx);

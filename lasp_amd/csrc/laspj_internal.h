@@ -33,6 +33,7 @@ struct laspj_ctx {
     int64_t tune_etf = 0;
     int64_t tune_etf_read = 0;
     int64_t tune_etf_seg = 0;
+    int64_t tune_etf_occ = 0;        // segment decoders: 1 = filled form, 2 = under-filled
     int64_t tune_reduce = 0;
     int64_t tune_product_rows = 0;
     int64_t tune_product_cols = 0;

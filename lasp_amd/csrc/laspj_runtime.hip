@@ -367,6 +367,11 @@ int laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value) {
                             "multiple of 256");
             ctx->tune_etf_seg = value;
             return LASPJ_OK;
+        case LASPJ_TUNE_ETF_OCC:
+            if (value < 0 || value > 2)
+                return fail(ctx, LASPJ_E_INVAL, "tuning: etf occupancy form must be 0, 1 or 2");
+            ctx->tune_etf_occ = value;
+            return LASPJ_OK;
         case LASPJ_TUNE_LIST_WALK:
             if (value < 0 || value > 3) return fail(ctx, LASPJ_E_INVAL, "tuning: list walk 0 .. 3");
             ctx->tune_list_walk = value;

@@ -25,6 +25,9 @@ L = ctx.L
 if os.environ.get("BIND_SEG"):                 # from_binary segment bytes (A/B)
     from lasp_amd import _lib  # noqa: E402
     ctx.set_tuning(_lib.TUNE_ETF_SEG, int(os.environ["BIND_SEG"]))
+if os.environ.get("BIND_OCC"):                 # segment decoder form (1 filled, 2 under-filled)
+    from lasp_amd import _lib  # noqa: E402
+    ctx.set_tuning(_lib.TUNE_ETF_OCC, int(os.environ["BIND_OCC"]))
 vs = [ctx.var("orset") for _ in range(many)]
 for v in vs:
     assert v.write(pa) == 0 and v.bind(pb) == (0, 1)

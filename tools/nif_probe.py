@@ -24,6 +24,8 @@ L = ctx.L
 from lasp_amd import _lib  # noqa: E402
 if os.environ.get("NIF_SEG"):                  # from_binary segment bytes (A/B)
     ctx.set_tuning(_lib.TUNE_ETF_SEG, int(os.environ["NIF_SEG"]))
+if os.environ.get("NIF_OCC"):                  # segment decoder form (1 filled, 2 under-filled)
+    ctx.set_tuning(_lib.TUNE_ETF_OCC, int(os.environ["NIF_OCC"]))
 if os.environ.get("NIF_ETF"):                  # writer variant (A/B; 5: the two-launch merge)
     ctx.set_tuning(_lib.TUNE_ETF_KERNEL, int(os.environ["NIF_ETF"]))
 op, on, vd = C.c_void_p(), C.c_uint64(), C.c_int32()
