@@ -108,6 +108,14 @@ extern "C" {
                                         laspj_list_intersection_set); for A/B            */
 int        laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value);
 
+/* What the context's last list merge did with the chunked walk (for its tests).  0 = the
+ * call did not launch it, 1 = it launched it and no replica fell back, 2 = a replica fell
+ * back to the one-wave walk (its walks did not meet).  Updated by laspj_list_merge,
+ * laspj_list_union and laspj_list_bind, and by the list variables' binds, which run
+ * laspj_list_bind's passes; every other call leaves it.  The value is on the host already
+ * (the launch shape, and the flag word these calls read back): asking costs nothing. */
+int        laspj_ctx_last_list_walk(const laspj_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

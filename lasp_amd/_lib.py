@@ -109,6 +109,7 @@ SIGNATURES = {
     "laspj_ctx_last_error": (C.c_char_p, [vp]),
     "laspj_ctx_synchronize": (i, [vp]),
     "laspj_ctx_set_tuning": (i, [vp, i, C.c_int64]),
+    "laspj_ctx_last_list_walk": (i, [vp]),
     "laspj_buf_create": (i, [vp, u64, vpp]),
     "laspj_buf_destroy": (i, [vp]),
     "laspj_buf_bytes": (u64, [vp]),

@@ -90,6 +90,9 @@ struct laspj_ctx {
     void* lspec = nullptr;
     uint64_t lspec_bytes = 0;
     bool lspec_dirty = false;
+    // laspj_ctx_last_list_walk: what the last list merge / union / bind did with it
+    // (0 not launched, 1 launched, 2 a replica fell back to the one-wave walk)
+    int last_list_walk = 0;
     // laspj_batch_bind_many_host's statuses (pinned, coherent: the kernel writes them there)
     void* many_h = nullptr;
     void* many_hd = nullptr;

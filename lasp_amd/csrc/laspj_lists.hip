@@ -2799,6 +2799,7 @@ static int merge_enqueue(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* a,
         spC = (uint32_t)((((uint64_t)a->known_e + spL - 1) / spL + kSpW - 1) / kSpW * kSpW);
         if (spL >= (1u << 20)) spC = 0;
     }
+    ctx->last_list_walk = spC ? 1 : 0;      // (the caller makes it 2 from the flag word)
     const uint64_t sz_fr = spC ? R * 4ull * m.ce_a : 0;
     // chunk maxima for the one-wave walk's long runs, when an input is known not to ascend
     const bool maxima = (spec || ctx->tune_list_walk == 3) && ctx->tune_list_walk != 1;
@@ -2933,6 +2934,7 @@ static int merge_impl(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* a,
     RK rk;
     if (int s = ranks(ctx, ord, a->kind != LASPJ_KIND_GSET_LIST, &rk, what)) return s;
     LGuard g(ctx);
+    ctx->last_list_walk = 0;
     const uint64_t R = a->replicas;
     void* dev = nullptr;
     if (laspj::dev_alloc(ctx, 8 * R, &dev) != hipSuccess) {
@@ -2950,7 +2952,10 @@ static int merge_impl(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* a,
         s = e != hipSuccess ? fail(ctx, LASPJ_E_DEVICE, "%s: readback: %s", what,
                                    hipGetErrorString(e))
                             : flag_status(ctx, f, what);
-        if (f & kInfoWalkFell) a->no_spec = b->no_spec = true;
+        if (f & kInfoWalkFell) {
+            a->no_spec = b->no_spec = true;
+            ctx->last_list_walk = 2;
+        }
     }
     laspj::dev_release(ctx, dev, 8 * R);
     if (s != LASPJ_OK) {
@@ -3400,6 +3405,7 @@ int laspj::list_bind_tail(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* c
     if (ws && (R != 1 || !W || !met))
         return fail(ctx, LASPJ_E_INVAL, "list_bind: a tail takes one replica and its waiters");
     LGuard g(ctx);
+    ctx->last_list_walk = 0;
     // both lists ascending (tried unless a list is known not to, and while the rank universe
     // is not much larger than the lists): the rank-indexed bind, two launches
     if (!cur->not_asc && !val->not_asc && ctx->tune_list_walk != 2 && R <= 1024 &&
@@ -3496,7 +3502,10 @@ int laspj::list_bind_tail(laspj_ctx* ctx, laspj_batch* dst, const laspj_batch* c
         s = e != hipSuccess ? fail(ctx, LASPJ_E_DEVICE, "list_bind: synchronise: %s",
                                    hipGetErrorString(e))
                             : flag_status(ctx, f, "list_bind");
-        if (f & kInfoWalkFell) cur->no_spec = val->no_spec = true;
+        if (f & kInfoWalkFell) {
+            cur->no_spec = val->no_spec = true;
+            ctx->last_list_walk = 2;
+        }
     }
     if (s != LASPJ_OK) {
         dst->known_e = dst->cap_e, dst->known_t = dst->cap_t;

@@ -395,6 +395,8 @@ int laspj_ctx_set_tuning(laspj_ctx* ctx, int knob, int64_t value) {
     }
 }
 
+int laspj_ctx_last_list_walk(const laspj_ctx* ctx) { return ctx ? ctx->last_list_walk : 0; }
+
 // ------------------------------------------------------------------------- buffers
 
 int laspj_buf_create(laspj_ctx* ctx, uint64_t bytes, laspj_buf** out) {

@@ -76,6 +76,11 @@ class Context:
     def set_tuning(self, knob: int, value: int):
         check(self.L.laspj_ctx_set_tuning(self.h, knob, value), self.h)
 
+    def last_list_walk(self) -> int:
+        """laspj_ctx_last_list_walk: 0 = the last list merge / union / bind did not launch
+        the chunked walk, 1 = it did and no replica fell back, 2 = a replica fell back."""
+        return int(self.L.laspj_ctx_last_list_walk(self.h))
+
     # -- factories
     def orset_batch(self, replicas: int, elements: int) -> "ORSetBatch":
         return ORSetBatch(self, replicas, elements)

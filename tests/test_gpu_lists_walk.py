@@ -85,18 +85,27 @@ def shapes_fix(out):
 
 def _walks(ctx, fn):
     """fn() with the default walk, the step walk (LASPJ_TUNE_LIST_WALK 1) and the chunked
-    walk over the chip (3, k_merge_spec: chunks of 256 rows, so these shapes span up to
-    32 chunks); the chunked result must equal the default one."""
+    walk over the chip (3, k_merge_spec) at its default chunk — 1024 rows: these shapes are
+    1..11 chunks in 1..3 workgroups, and those that settle do so in 2 rounds (DESIGN.md
+    gives the model's verdict per shape) — and at LASPJ_TUNE_LIST_CHUNK 256 (up to 41
+    chunks in 11 workgroups); both chunked results must equal the default one.  The walk's
+    corrections over rounds, its fall-backs and which path ran are
+    test_gpu_spec_walk.py's."""
     from lasp_amd import _lib
     got = fn()
     try:
         ctx.set_tuning(_lib.TUNE_LIST_WALK, 3)
         chunked = fn()
+        ctx.set_tuning(_lib.TUNE_LIST_CHUNK, 256)
+        chunked256 = fn()
+        ctx.set_tuning(_lib.TUNE_LIST_CHUNK, 0)
         ctx.set_tuning(_lib.TUNE_LIST_WALK, 1)
         step = fn()
     finally:
+        ctx.set_tuning(_lib.TUNE_LIST_CHUNK, 0)
         ctx.set_tuning(_lib.TUNE_LIST_WALK, 0)
     assert exact_eq(chunked, got)
+    assert exact_eq(chunked256, got)
     return got, step
 
 
