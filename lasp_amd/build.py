@@ -20,7 +20,8 @@ SOURCES = ["laspj_runtime.hip", "laspj_kernels.hip", "laspj_combinators.hip",
            "laspj_nif_waiters.hip", "laspj_nif_process.hip", "laspj_nif_lvars.hip",
            "laspj_nif_maps.hip", "laspj_host.cpp", "laspj_list_etf.cpp",
            "laspj_counters.hip", "laspj_counter_host.cpp", "laspj_process.hip",
-           "laspj_reads.hip", "laspj_reads_host.cpp", "laspj_lvars.hip"]
+           "laspj_reads.hip", "laspj_reads_host.cpp", "laspj_lvars.hip",
+           "laspj_dict_tables.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-Wall", "-Wno-unused-value", "-Wno-unused-result"]

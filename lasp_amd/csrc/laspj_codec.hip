@@ -30,13 +30,8 @@
 #include <new>
 #include <vector>
 
+#include "laspj_dict_tables.h"
 #include "laspj_internal.h"
-
-// a token image that is BINARY_EXT of exactly the rest of its bytes
-static inline bool tok_is_binary(const uint8_t* p, uint32_t len) {
-    return len >= 5u && p[0] == 109 &&
-           (((uint32_t)p[1] << 24) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 8) | p[4]) == len - 5u;
-}
 
 struct laspj_etf_dict {
     laspj_ctx* ctx = nullptr;
@@ -98,10 +93,10 @@ struct laspj_etf_dict {
     uint32_t gs_in = 0;
     // host-side state for laspj::etf_dict_patch (dictionaries built with token headroom,
     // the NIF path's): slot -> rank, each token slot's padded image offset (0xFFFFFFFF:
-    // none), where the patched arrays sit in the block, the padded-image area's use
+    // none), where the arrays sit in the block, the padded-image area's use
     bool patchable = false;
     std::vector<uint32_t> h_rank, h_tpoff;
-    uint64_t o_mask = 0, o_tord = 0, o_tpad = 0, o_tdesc = 0, o_rpad = 0, o_rd = 0;
+    laspj::DictLayout lay;
     uint64_t tpad_used = 0, tpad_cap = 0;
 };
 
@@ -1920,11 +1915,9 @@ __global__ __launch_bounds__(kBlock) void k_orset_etf_read_serial(const uint8_t*
 // is "the one rank whose template matches, if it comes after the previous one").
 
 constexpr uint32_t kBWin = 4096;         // batched decode window
-constexpr uint32_t kBuckets = 1024;      // token buckets per element
-// an element's key when no bucket window separates its tokens: the batch paths find no
-// bucket (its table entries are 0xFFFF) and leave it to decode_elems, which matches its
-// records against each template
-constexpr uint32_t kNoBuckets = 0x80000000u;
+// (kBuckets token buckets per element, an element's key kNoBuckets when no bucket window
+// separates its tokens, and where the tables below sit in the block, RdLayout:
+// laspj_dict_tables.h)
 
 struct ReadTabs {
     const uint4* desc;      // by rank: slot, header length, word | shift << 8, token ranks
@@ -1933,9 +1926,6 @@ struct ReadTabs {
     const uint8_t* ros;     // by rank r, token slot s: its token rank at 64 r + s (0xFF: none)
     NewTokArgs nt;          // (out null: unseen tokens answer UNKNOWN_TERM)
 };
-
-// bytes of the ReadTabs tables: desc, hdr, tb, ros
-inline uint64_t rd_bytes(uint64_t E, uint64_t RK) { return E * (16 + 64 + 2 * RK + 64) + 64; }
 
 // words of staged bytes [o, o + L) (L <= 48), zero past L; reads 52 bytes from o & ~3
 __device__ __forceinline__ void rec_words(const uint8_t* buf, uint32_t o, uint32_t L,
@@ -2186,13 +2176,6 @@ struct HdrHash {
     uint32_t many = 0;     // many-token dictionaries: element batches (read_batch_many)
 };
 
-// the header-template hash (host and device agree): ceil(hl / 4) words, bytes >= hl zero
-__host__ __device__ inline uint32_t hdr_mix(uint32_t h, uint32_t v) {
-    h ^= v;
-    h *= 0x9E3779B1u;
-    return h ^ (h >> 16);
-}
-
 // Element batches, for dictionaries with few token slots per element (tok_max <= 8,
 // e.g. the ad counter's 3-replica tokens): one element at a time leaves 60 of 64 lanes
 // idle, so the wave walks up to 64 whole elements before checking any record.  Lane i
@@ -2207,7 +2190,7 @@ __host__ __device__ inline uint32_t hdr_mix(uint32_t h, uint32_t v) {
 // element-at-a-time path decodes from there and gives the status.  What a batch commits
 // is what that path would accept, with the same cells (element images are
 // self-delimiting and distinct, so the header match is the scan's first match).
-constexpr uint32_t kSmallTok = 8;
+
 // the element-batch decoders (SMALL) for a dictionary whose elements mostly hold at most
 // kSmallTok tokens: an element with more fails its batch and is decoded on its own by the
 // general path (a few hot elements — re-added again and again — no longer move every
@@ -3834,12 +3817,6 @@ int reserve_scratch(laspj_ctx* ctx, uint64_t need) {
 
 __device__ __forceinline__ uint32_t be32(const uint8_t* p) {
     return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
-}
-
-__device__ __host__ __forceinline__ uint32_t fnv1a(const uint8_t* p, uint32_t n) {
-    uint32_t h = 2166136261u;
-    for (uint32_t i = 0; i < n; ++i) h = (h ^ p[i]) * 16777619u;
-    return h;
 }
 
 // extent of the external term at p within n bytes: its length; 0 when it runs past n or
@@ -5540,6 +5517,22 @@ int etf_write_enqueue(laspj_ctx* ctx, const laspj_batch* b, const laspj_etf_dict
     return LASPJ_OK;
 }
 
+// the context's pinned dictionary staging made to hold `need` bytes (a new one of `want`
+// bytes: the caller's growth rule); ctx->mu held, the stream idle
+bool grow_dstage(laspj_ctx* ctx, uint64_t need, uint64_t want) {
+    if (ctx->dstage_bytes >= need) return true;
+    if (ctx->dstage) hipHostFree(ctx->dstage);
+    ctx->dstage = nullptr;
+    ctx->dstage_bytes = 0;
+    if (hipHostMalloc(&ctx->dstage, want, hipHostMallocDefault) != hipSuccess) {
+        hipGetLastError();
+        ctx->dstage = nullptr;
+        return false;
+    }
+    ctx->dstage_bytes = want;
+    return true;
+}
+
 }  // namespace laspj
 
 using laspj::fail;
@@ -5554,341 +5547,17 @@ static int etf_dict_create_body(laspj_ctx* ctx, uint32_t E, const uint8_t* elem_
                                 const uint8_t* tok_blob, const uint32_t* tok_off,
                                 const uint8_t* tok_order, uint32_t tok_headroom,
                                 laspj_etf_dict** out, bool trusted = false) {
-    // (trusted: arrays the library exported itself from its host dictionary, where offsets
-    // ascend, the order is a permutation and token orders name exactly the used slots by
-    // construction — those checks, passes over every slot, are left out)
+    // (trusted: arrays the library exported itself from its host dictionary)
     if (!ctx || !out || !elem_off || !elem_order || (!elem_blob && elem_off[E]))
         return fail(ctx, LASPJ_E_INVAL, "etf_dict_create: null argument");
     *out = nullptr;
-    if (E == 0) return fail(ctx, LASPJ_E_SHAPE, "etf_dict_create: no element slots");
-    const bool toks = tok_off != nullptr;
-    if (toks && (!tok_order || (!tok_blob && tok_off[64ull * E])))
-        return fail(ctx, LASPJ_E_INVAL, "etf_dict_create: token arrays incomplete");
-    // host-side validation and derived arrays
-    std::vector<uint8_t> ebyte(E, 0);
-    std::vector<uint64_t> tmask(E, 0);
-    {
-        std::vector<uint8_t> ranked(trusted ? 0 : E, 0);    // (the order must be a permutation)
-        for (uint32_t e = 0; e < E; ++e) {
-            if (!trusted &&
-                (elem_off[e + 1] < elem_off[e] || elem_order[e] >= E || ranked[elem_order[e]]++))
-                return fail(ctx, LASPJ_E_RANGE, "etf_dict_create: element offsets / order invalid");
-            ebyte[e] = elem_off[e + 1] - elem_off[e] == 2 && elem_blob[elem_off[e]] == 97;
-        }
-    }
-    uint32_t uniform = 0;
-    bool mixed = false, binall = true;
-    // 16-byte-aligned copies of every image (the write kernels load them 16 B at a time);
-    // an empty token slot keeps offset ~0u (the patch's "no image" mark)
-    auto pad16 = [](uint64_t x) { return (x + 15ull) & ~15ull; };
-    std::vector<uint32_t> epoff(E), tpoff;
-    uint64_t epad_n = 0, tpad_n = 0;
-    if (toks) {
-        uint32_t bad = 0;                             // (branch-free: it vectorises)
-        for (uint64_t t = 0; !trusted && t < 64ull * E; ++t) bad |= tok_off[t + 1] < tok_off[t];
-        if (bad) return fail(ctx, LASPJ_E_RANGE, "etf_dict_create: token offsets decrease");
-        tpoff.assign(64ull * E, 0xFFFFFFFFu);
-        for (uint32_t e = 0; e < E; ++e) {
-            const uint32_t* to = tok_off + 64ull * e;
-            if (to[64] == to[0]) continue;            // no tokens: the common case, one test
-            uint64_t m = 0;
-            for (uint32_t k = 0; k < 64 && to[k] != to[64]; ++k) {   // (to the last token)
-                const uint32_t len = to[k + 1] - to[k];
-                if (!len) continue;
-                m |= 1ull << k;
-                if (!uniform) uniform = len;
-                else if (uniform != len) mixed = true;
-                if (binall) binall = tok_is_binary(tok_blob + to[k], len);
-                tpoff[64ull * e + k] = (uint32_t)tpad_n;
-                tpad_n += pad16(len);
-            }
-            tmask[e] = m;
-        }
-        for (uint32_t e = 0; e < E && !trusted; ++e) {
-            uint64_t seen = 0;
-            for (int j = 0; j < 64; ++j) {
-                uint8_t k = tok_order[64ull * e + j];
-                if (k >= 64) break;
-                if (!((tmask[e] >> k) & 1ull) || ((seen >> k) & 1ull))
-                    return fail(ctx, LASPJ_E_RANGE,
-                                "etf_dict_create: token order of element %u names slot %u "
-                                "twice or without an image", e, k);
-                seen |= 1ull << k;
-            }
-            if (seen != tmask[e])
-                return fail(ctx, LASPJ_E_RANGE,
-                            "etf_dict_create: token order of element %u misses a slot", e);
-        }
-    }
-    uint32_t big = 0;
-    for (uint32_t e = 0; e < E; ++e) big += __builtin_popcountll(tmask[e]) > 8 ? 1u : 0u;
-    const bool bin = toks && !mixed && uniform >= 5u && binall;
-    const uint64_t eblob = elem_off[E];
-    for (uint32_t e = 0; e < E; ++e) {
-        epoff[e] = (uint32_t)epad_n;
-        epad_n += pad16(elem_off[e + 1] - elem_off[e]);
-    }
-    epad_n += 48;                 // a 48-byte load past the last image stays inside
-    tpad_n += 48;
-    if (epad_n >= (1ull << 32) || tpad_n >= (1ull << 32))
-        return fail(ctx, LASPJ_E_RANGE, "etf_dict_create: images exceed 4 GiB");
-    std::vector<uint8_t> epad(epad_n, 0), tpad(tpad_n, 0);
-    for (uint32_t e = 0; e < E; ++e)
-        std::copy(elem_blob + elem_off[e], elem_blob + elem_off[e + 1], epad.begin() + epoff[e]);
-    uint32_t tok_max = 0;
-    for (uint32_t x = 0; x < E; ++x)
-        tok_max = std::max(tok_max, (uint32_t)__builtin_popcountll(tmask[x]));
-    // (past 8 the head-room grows with the count: a hot element re-added again and again —
-    // add_elem never collects a token — then rebuilds the images every count / 2 adds, not
-    // every tok_headroom)
-    if (tok_headroom && toks)
-        tok_max = tok_max <= 8 ? std::min(8u, tok_max + tok_headroom)
-                               : std::min(64u, tok_max + std::max(tok_headroom, tok_max / 2));
-    // the writer's descriptors by (element, term rank), tok_max per element (not 64: a
-    // rebuild then builds and uploads what the elements hold)
-    std::vector<uint64_t> tdesc(toks ? (uint64_t)tok_max * E : 0, 0xFFull);
-    for (uint64_t e = 0; toks && e < E; ++e)
-        for (uint32_t j = 0; j < tok_max; ++j) {
-            const uint64_t k = tok_order[64ull * e + j];
-            if (k >= 64) break;
-            const uint64_t t = 64ull * e + k, L = tok_off[t + 1] - tok_off[t];
-            tdesc[e * tok_max + j] =
-                k | (std::min<uint64_t>(L, 0xFFFFFFull) << 8) | ((uint64_t)tpoff[t] << 32);
-        }
-    // room for token images appended by etf_dict_patch
-    const uint64_t tpad_cap = tpad_n + (tok_headroom && toks ? std::max<uint64_t>(tpad_n / 4, 1ull << 16) : 0);
-    // record templates (uniform token images only): 104 2 <image> per (element, term rank),
-    // and 104 2 <elem image> 108 per element
-    const uint32_t rec_len = (toks && !mixed && uniform && uniform + 2u <= 48u) ? uniform + 2u : 0u;
-    const uint64_t rec_stride = pad16(rec_len);
-    uint64_t ehdr_max = 0;
-    std::vector<uint8_t> rpad, hpad;
-    std::vector<uint32_t> hpoff;
-    std::vector<uint8_t> rd;
-    bool hashed = rec_len != 0;
-    if (rec_len) {
-        rpad.assign((uint64_t)E * tok_max * rec_stride + 48, 0);
-        for (uint64_t e = 0; e < E; ++e)
-            for (uint32_t j = 0; j < tok_max; ++j) {
-                const uint8_t k = tok_order[64ull * e + j];
-                if (k >= 64) break;
-                const uint64_t t = 64ull * e + k;
-                uint8_t* r = rpad.data() + (e * tok_max + j) * rec_stride;
-                r[0] = 104;
-                r[1] = 2;
-                std::copy(tok_blob + tok_off[t], tok_blob + tok_off[t + 1], r + 2);
-            }
-        hpoff.resize(E);
-        uint64_t hn = 0;
-        for (uint32_t e = 0; e < E; ++e) {
-            hpoff[e] = (uint32_t)hn;
-            hn += pad16(elem_off[e + 1] - elem_off[e] + 3ull);
-            ehdr_max = std::max<uint64_t>(ehdr_max, elem_off[e + 1] - elem_off[e] + 3ull);
-        }
-        if (hn + 48 >= (1ull << 32) || rpad.size() >= (1ull << 40))
-            return fail(ctx, LASPJ_E_RANGE, "etf_dict_create: record templates too large");
-        hpad.assign(hn + 48, 0);
-        for (uint32_t e = 0; e < E; ++e) {
-            uint8_t* h = hpad.data() + hpoff[e];
-            h[0] = 104;
-            h[1] = 2;
-            std::copy(elem_blob + elem_off[e], elem_blob + elem_off[e + 1], h + 2);
-            h[2 + elem_off[e + 1] - elem_off[e]] = 108;
-        }
-        // from_binary tables by element rank: per element a template word and shift
-        // that put its tokens in distinct buckets (none found: serial decode)
-        rd.assign(laspj::rd_bytes(E, tok_max), 0);
-        uint32_t* desc = reinterpret_cast<uint32_t*>(rd.data());
-        uint8_t* hdr = rd.data() + 16ull * E;
-        uint16_t* tbk = reinterpret_cast<uint16_t*>(hdr + 64ull * E);
-        uint8_t* ros = reinterpret_cast<uint8_t*>(tbk + (uint64_t)E * tok_max);
-        std::memset(ros, 0xFF, 64ull * E);
-        const uint32_t nwords = rec_len / 4;     // whole words of the template
-        std::vector<uint32_t> keys;
-        // (by slot, each slot's rank looked up: the slot-indexed sources read in order)
-        std::vector<uint32_t> rank_of(E);
-        for (uint32_t r = 0; r < E; ++r) rank_of[elem_order[r]] = r;
-        for (uint32_t e = 0; e < E && hashed; ++e) {
-            const uint64_t r = rank_of[e];
-            const uint32_t hl = elem_off[e + 1] - elem_off[e] + 3u;
-            uint32_t cnt = 0;
-            while (cnt < tok_max && tok_order[64ull * e + cnt] < 64) ++cnt;
-            desc[4 * r] = e;
-            desc[4 * r + 1] = hl;
-            desc[4 * r + 3] = cnt;
-            std::copy(hpad.data() + hpoff[e], hpad.data() + hpoff[e] + std::min(hl, 64u),
-                      hdr + 64 * r);
-            for (uint32_t j = 0; j < cnt; ++j) ros[64 * r + tok_order[64ull * e + j]] = (uint8_t)j;
-            if (cnt == 0) continue;
-            bool placed = false;
-            for (uint32_t wi = nwords; wi-- > 0 && !placed;) {
-                keys.resize(cnt);
-                uint32_t diff = 0;                // the bits where some token differs
-                for (uint32_t j = 0; j < cnt; ++j) {
-                    std::memcpy(&keys[j], rpad.data() + ((uint64_t)e * tok_max + j) * rec_stride +
-                                               4 * wi, 4);
-                    diff |= keys[j] ^ keys[0];
-                }
-                if (cnt > 1 && !diff) continue;     // one word for all: no window parts them
-                for (uint32_t sh = 0; sh + 10 <= 32 && !placed; ++sh) {
-                    // (a window without a differing bit puts every token in one bucket)
-                    if (cnt > 1 && !((diff >> sh) & (laspj::kBuckets - 1u))) continue;
-                    bool ok = true;
-                    if (cnt <= 16) {
-                        for (uint32_t j = 1; j < cnt && ok; ++j) {
-                            const uint32_t bj = (keys[j] >> sh) & (laspj::kBuckets - 1u);
-                            for (uint32_t i = 0; i < j && ok; ++i)
-                                ok = ((keys[i] >> sh) & (laspj::kBuckets - 1u)) != bj;
-                        }
-                    } else {
-                        uint64_t seen[laspj::kBuckets / 64] = {};
-                        for (uint32_t j = 0; j < cnt && ok; ++j) {
-                            const uint32_t bk = (keys[j] >> sh) & (laspj::kBuckets - 1u);
-                            ok = !((seen[bk / 64] >> (bk % 64)) & 1ull);
-                            seen[bk / 64] |= 1ull << (bk % 64);
-                        }
-                    }
-                    if (!ok) continue;
-                    placed = true;
-                    desc[4 * r + 2] = wi | (sh << 8);
-                    for (uint32_t j = 0; j < cnt; ++j)
-                        tbk[r * tok_max + j] = (uint16_t)((keys[j] >> sh) & (laspj::kBuckets - 1u));
-                }
-            }
-            if (!placed) {
-                // no one 10-bit window tells this element's tokens apart (tokens that agree
-                // everywhere but where others also agree): its records are matched against
-                // each of its templates instead (kNoBuckets; rare, and only this element)
-                desc[4 * r + 2] = laspj::kNoBuckets;
-                for (uint32_t j = 0; j < cnt; ++j) tbk[r * tok_max + j] = 0xFFFFu;
-            }
-        }
-        if (!hashed) rd.clear();
-    }
-    // segment mode: header template (<= 64 bytes) -> rank, hashed as the device hashes
-    std::vector<uint32_t> htab;
-    uint64_t hlens = 0;
-    if (hashed) {
-        uint64_t cap = 64;
-        while (cap < 2ull * E) cap <<= 1;
-        htab.assign(cap, 0);
-        const uint8_t* hdr = rd.data() + 16ull * E;
-        const uint32_t* desc = reinterpret_cast<const uint32_t*>(rd.data());
-        for (uint64_t r = 0; r < E; ++r) {
-            const uint32_t hl = desc[4 * r + 1];
-            if (hl < 4 || hl > 64) continue;
-            uint32_t h = hl * 0x85EBCA6Bu;
-            for (uint32_t i = 0; 4 * i < hl; ++i) {         // ceil(hl / 4) words
-                uint32_t v;
-                std::memcpy(&v, hdr + 64 * r + 4 * i, 4);   // zero past hl
-                h = laspj::hdr_mix(h, v);
-            }
-            uint64_t i = h & (cap - 1);
-            while (htab[i]) i = (i + 1) & (cap - 1);
-            htab[i] = (uint32_t)r + 1u;
-            hlens |= 1ull << (hl - 1);
-        }
-    }
-    for (uint64_t e = 0; toks && e < E; ++e)
-        for (uint64_t m = tmask[e]; m; m &= m - 1) {          // the slots holding a token
-            const uint64_t t = 64ull * e + __builtin_ctzll(m);
-            std::copy(tok_blob + tok_off[t], tok_blob + tok_off[t + 1], tpad.begin() + tpoff[t]);
-        }
-    // G-Set from_binary tables: ranks (equal terms share one), image hash, byte values.
-    // Not for the library's own OR-Set namespaces (trusted, with tokens): their payloads
-    // are OR-Set images only, and the tables cost a term comparison per slot per rebuild
-    const bool gs = !(trusted && toks);
-    uint64_t gs_cap = 64;
-    while (gs && gs_cap < 2ull * E) gs_cap <<= 1;
-    auto al = [](uint64_t x) { return (x + 255ull) & ~255ull; };
-    std::vector<uint32_t> gs_rank(gs ? E : 0, 0), gs_byte(256, 0), gs_htab;
-    if (gs) {
-        uint32_t rk = 0;
-        for (uint32_t k = 0; k < E; ++k) {
-            const uint32_t e = elem_order[k];
-            if (k) {
-                const uint32_t p = elem_order[k - 1];
-                int c = 1;
-                const bool both = elem_off[e + 1] > elem_off[e] && elem_off[p + 1] > elem_off[p];
-                if (!both || laspj_term_compare(elem_blob + elem_off[p], elem_off[p + 1] - elem_off[p],
-                                                elem_blob + elem_off[e], elem_off[e + 1] - elem_off[e],
-                                                &c) != LASPJ_OK)
-                    c = 1;
-                if (c != 0) ++rk;
-            }
-            gs_rank[e] = rk;
-        }
-        const uint64_t cap = gs_cap;
-        gs_htab.assign(cap, 0);
-        for (uint32_t e = 0; e < E; ++e) {
-            const uint32_t n = elem_off[e + 1] - elem_off[e];
-            if (!n) continue;
-            const uint8_t* img = elem_blob + elem_off[e];
-            if (n == 2 && img[0] == 97 && !gs_byte[img[1]]) gs_byte[img[1]] = e + 1;
-            uint64_t i = laspj::fnv1a(img, n) & (cap - 1);
-            bool dup = false;
-            while (gs_htab[i]) {
-                const uint32_t o = gs_htab[i] - 1;
-                if (elem_off[o + 1] - elem_off[o] == n &&
-                    std::memcmp(elem_blob + elem_off[o], img, n) == 0)
-                    dup = true;                  // an image twice: the first slot keeps it
-                if (dup) break;
-                i = (i + 1) & (cap - 1);
-            }
-            if (!dup) gs_htab[i] = e + 1;
-        }
-    }
-    // integer elements by value (minimal images: SMALL_INTEGER for 0..255, INTEGER past it)
-    std::vector<uint64_t> gs_itab;
-    int64_t ilo = 0;
-    if (gs) {
-        int64_t lo = INT64_MAX, hi = INT64_MIN;
-        uint64_t cnt = 0;
-        auto int_of = [&](uint32_t e, int64_t* v) {
-            const uint32_t n = elem_off[e + 1] - elem_off[e];
-            const uint8_t* img = elem_blob + elem_off[e];
-            if (n == 2 && img[0] == 97) {
-                *v = img[1];
-                return true;
-            }
-            if (n == 5 && img[0] == 98) {
-                *v = (int32_t)((uint32_t)img[1] << 24 | (uint32_t)img[2] << 16 |
-                               (uint32_t)img[3] << 8 | img[4]);
-                return *v < 0 || *v > 255;
-            }
-            return false;
-        };
-        for (uint32_t e = 0; e < E; ++e) {
-            int64_t v;
-            if (int_of(e, &v)) lo = std::min(lo, v), hi = std::max(hi, v), ++cnt;
-        }
-        if (cnt && (uint64_t)(hi - lo) < std::max<uint64_t>(4 * cnt, 1ull << 16)) {
-            ilo = lo;
-            gs_itab.assign((uint64_t)(hi - lo) + 1, 0);
-            for (uint32_t e = 0; e < E; ++e) {
-                int64_t v;
-                if (int_of(e, &v) && !gs_itab[v - lo])      // one value twice: the first slot
-                    gs_itab[v - lo] = (e + 1ull) | ((uint64_t)gs_rank[e] << 32);
-            }
-        }
-    }
-    // on the device: the token offsets only for mixed image lengths (the size pass reads
-    // them then); the token images themselves and their padded offsets never (the kernels
-    // read the padded copies through tok_desc) — 64 E-slot arrays the NIF path's rebuilds
-    // would otherwise stage and copy every time
-    const bool dev_toff = toks && mixed;
-    const uint64_t o_eoff = 0, o_eord = o_eoff + al(4ull * (E + 1)), o_eb = o_eord + al(4ull * E),
-                   o_mask = o_eb + al(E), o_toff = o_mask + al(8ull * E),
-                   o_tord = o_toff + (dev_toff ? al(4ull * (64ull * E + 1)) : 0),
-                   o_eblob = o_tord + (toks ? al(64ull * E) : 0), o_tblob = o_eblob + al(eblob + 1),
-                   o_epoff = o_tblob, o_tpoff = o_epoff + al(4ull * E),
-                   o_epad = o_tpoff, o_tpad = o_epad + al(epad_n),
-                   o_tdesc = o_tpad + al(tpad_cap), o_rpad = o_tdesc + al(8ull * tdesc.size() + 8),
-                   o_hpad = o_rpad + al(rpad.size()), o_hpoff = o_hpad + al(hpad.size()),
-                   o_rd = o_hpoff + al(4ull * hpoff.size() + 4),
-                   o_htab = o_rd + al(rd.size() + 8), o_gsh = o_htab + al(4ull * htab.size() + 4),
-                   o_gsr = o_gsh + al(4ull * gs_cap), o_gsb = o_gsr + al(4ull * (gs ? E : 0)),
-                   o_gsi = o_gsb + al(4ull * (gs ? 256 : 0)), bytes = o_gsi + al(8ull * gs_itab.size() + 8);
+    // validation and every derived table, on the host (laspj_dict_tables.cpp)
+    const laspj::DictSource src{E, elem_blob, elem_off, elem_order, tok_blob, tok_off, tok_order};
+    laspj::DictTables t;
+    if (int s = laspj::dict_tables_build(src, tok_headroom, trusted, &t))
+        return fail(ctx, s, "%s", t.err.c_str());
+    const laspj::DictLayout& L = t.lay;
+    const uint64_t bytes = L.bytes;
     auto* d = new (std::nothrow) laspj_etf_dict;
     if (!d) return fail(ctx, LASPJ_E_NOMEM, "etf_dict_create: host allocation");
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -5902,126 +5571,74 @@ static int etf_dict_create_body(laspj_ctx* ctx, uint32_t E, const uint8_t* elem_
     }
     d->block_bytes = bytes;
     char* base = static_cast<char*>(d->block);
-    // every array staged into one pinned host image of the block (the context's, grow-only;
+    // every array written into one pinned host image of the block (the context's, grow-only;
     // the previous image's copy has finished before it is rewritten), then one async copy
     hipStreamSynchronize(ctx->stream);
-    if (ctx->dstage_bytes < bytes) {
-        if (ctx->dstage) hipHostFree(ctx->dstage);
-        ctx->dstage = nullptr;
-        ctx->dstage_bytes = 0;
-        const uint64_t want = std::max<uint64_t>(bytes, 1ull << 20) + bytes / 4;
-        if (hipHostMalloc(&ctx->dstage, want, hipHostMallocDefault) != hipSuccess) {
-            hipGetLastError();
-            ctx->dstage = nullptr;
-            laspj::dev_release(ctx, d->block, bytes);
-            delete d;
-            return fail(ctx, LASPJ_E_NOMEM, "etf_dict_create: pinned staging");
-        }
-        ctx->dstage_bytes = want;
+    if (!laspj::grow_dstage(ctx, bytes, std::max<uint64_t>(bytes, 1ull << 20) + bytes / 4)) {
+        laspj::dev_release(ctx, d->block, bytes);
+        delete d;
+        return fail(ctx, LASPJ_E_NOMEM, "etf_dict_create: pinned staging");
     }
-    char* img = static_cast<char*>(ctx->dstage);
-    // the arrays, then zeros in the alignment gaps between them (nothing reads them; kept
-    // deterministic) — no zero fill of the whole image first
-    std::vector<std::pair<uint64_t, uint64_t>> spans;
-    auto up = [&](uint64_t off, const void* src, uint64_t n) {
-        if (n) std::memcpy(img + off, src, n);
-        spans.emplace_back(off, n);
-        return hipSuccess;
-    };
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = up(o_eoff, elem_off, 4ull * (E + 1));
-    if (e == hipSuccess) e = up(o_eord, elem_order, 4ull * E);
-    if (e == hipSuccess) e = up(o_eb, ebyte.data(), E);
-    if (e == hipSuccess) e = up(o_mask, tmask.data(), 8ull * E);
-    if (e == hipSuccess && dev_toff) e = up(o_toff, tok_off, 4ull * (64ull * E + 1));
-    if (e == hipSuccess && toks) e = up(o_tord, tok_order, 64ull * E);
-    if (e == hipSuccess) e = up(o_eblob, elem_blob, eblob);
-
-    if (e == hipSuccess) e = up(o_epoff, epoff.data(), 4ull * E);
-
-    if (e == hipSuccess) e = up(o_epad, epad.data(), epad_n);
-    if (e == hipSuccess && toks) e = up(o_tpad, tpad.data(), tpad_n);
-    if (e == hipSuccess && toks) e = up(o_tdesc, tdesc.data(), 8ull * tdesc.size());
-    if (e == hipSuccess && rec_len) e = up(o_rpad, rpad.data(), rpad.size());
-    if (e == hipSuccess && rec_len) e = up(o_hpad, hpad.data(), hpad.size());
-    if (e == hipSuccess && rec_len) e = up(o_hpoff, hpoff.data(), 4ull * hpoff.size());
-    if (e == hipSuccess && hashed) e = up(o_rd, rd.data(), rd.size());
-    if (e == hipSuccess && hashed) e = up(o_htab, htab.data(), 4ull * htab.size());
-    if (e == hipSuccess && gs) e = up(o_gsh, gs_htab.data(), 4ull * gs_htab.size());
-    if (e == hipSuccess && gs) e = up(o_gsr, gs_rank.data(), 4ull * E);
-    if (e == hipSuccess && gs) e = up(o_gsb, gs_byte.data(), 4ull * 256);
-    if (e == hipSuccess && !gs_itab.empty()) e = up(o_gsi, gs_itab.data(), 8ull * gs_itab.size());
-    if (e == hipSuccess) {
-        std::sort(spans.begin(), spans.end());
-        uint64_t at = 0;
-        for (const auto& sp : spans) {
-            if (sp.first > at) std::memset(img + at, 0, sp.first - at);
-            at = std::max(at, sp.first + sp.second);
-        }
-        if (bytes > at) std::memset(img + at, 0, bytes - at);
-        e = hipMemcpyAsync(base, img, bytes, hipMemcpyHostToDevice, ctx->stream);
-    }
+    laspj::dict_tables_write(src, t, ctx->dstage);
+    const hipError_t e = hipMemcpyAsync(base, ctx->dstage, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) {
         laspj::dev_release(ctx, d->block, bytes);
         delete d;
         return fail(ctx, LASPJ_E_DEVICE, "etf_dict_create: upload: %s", hipGetErrorString(e));
     }
+    auto at = [base](uint64_t off) { return reinterpret_cast<const uint8_t*>(base + off); };
+    auto at32 = [base](uint64_t off) { return reinterpret_cast<const uint32_t*>(base + off); };
+    auto at64 = [base](uint64_t off) { return reinterpret_cast<const uint64_t*>(base + off); };
     d->ctx = ctx;
     d->elements = E;
-    d->has_tokens = toks;
-    d->tok_uniform = mixed ? 0u : uniform;
-    d->tok_max = tok_max;
-    d->rec_len = rec_len;
-    d->bin_tokens = bin && rec_len != 0;
-    d->big_elems = big;
-    d->ehdr_max = (uint32_t)std::min<uint64_t>(ehdr_max, 0xFFFFFFFFull);
-    d->rec_stride = (uint32_t)rec_stride;
-    d->rec_pad = rec_len ? reinterpret_cast<const uint8_t*>(base + o_rpad) : nullptr;
-    d->ehdr_pad = rec_len ? reinterpret_cast<const uint8_t*>(base + o_hpad) : nullptr;
-    d->ehdr_poff = rec_len ? reinterpret_cast<const uint32_t*>(base + o_hpoff) : nullptr;
-    if (hashed) {
-        const uint8_t* t = reinterpret_cast<const uint8_t*>(base + o_rd);
-        d->rd_desc = t;
-        d->rd_hdr = t + 16ull * E;
-        d->rd_tb = reinterpret_cast<const uint16_t*>(t + 16ull * E + 64ull * E);
-        d->rd_ros = reinterpret_cast<const uint8_t*>(d->rd_tb + (uint64_t)E * tok_max);
-        d->rd_htab = reinterpret_cast<const uint32_t*>(base + o_htab);
-        d->rd_hmask = (uint32_t)(htab.size() - 1);
-        d->rd_hlens = hlens;
+    d->has_tokens = t.toks;
+    d->tok_uniform = t.tok_uniform;
+    d->tok_max = t.tok_max;
+    d->rec_len = t.rec_len;
+    d->bin_tokens = t.bin_tokens;
+    d->big_elems = t.big_elems;
+    d->ehdr_max = t.ehdr_max;
+    d->rec_stride = t.rec_stride;
+    if (t.rec_len) {
+        const laspj::RdLayout rl(E, t.tok_max);
+        d->rec_pad = at(L.rpad);
+        d->ehdr_pad = at(L.hpad);
+        d->ehdr_poff = at32(L.hpoff);
+        d->rd_desc = at(L.rd + rl.desc);
+        d->rd_hdr = at(L.rd + rl.hdr);
+        d->rd_tb = reinterpret_cast<const uint16_t*>(base + L.rd + rl.tb);
+        d->rd_ros = at(L.rd + rl.ros);
+        d->rd_htab = at32(L.htab);
+        d->rd_hmask = t.rd_hmask;
+        d->rd_hlens = t.rd_hlens;
     }
-    d->gs_htab = gs ? reinterpret_cast<const uint32_t*>(base + o_gsh) : nullptr;
-    d->gs_hmask = (uint32_t)(gs_cap - 1);
-    d->gs_rank = gs ? reinterpret_cast<const uint32_t*>(base + o_gsr) : nullptr;
-    d->gs_byte = gs ? reinterpret_cast<const uint32_t*>(base + o_gsb) : nullptr;
-    d->gs_itab = gs_itab.empty() ? nullptr : reinterpret_cast<const uint64_t*>(base + o_gsi);
-    d->gs_ilo = ilo;
-    d->gs_in = (uint32_t)gs_itab.size();
-    d->elem_off = reinterpret_cast<const uint32_t*>(base + o_eoff);
-    d->elem_order = reinterpret_cast<const uint32_t*>(base + o_eord);
-    d->elem_byte = reinterpret_cast<const uint8_t*>(base + o_eb);
-    d->tok_mask = reinterpret_cast<const uint64_t*>(base + o_mask);
-    d->tok_off = dev_toff ? reinterpret_cast<const uint32_t*>(base + o_toff) : nullptr;
-    d->tok_order = toks ? reinterpret_cast<const uint8_t*>(base + o_tord) : nullptr;
-    d->elem_blob = reinterpret_cast<const uint8_t*>(base + o_eblob);
-    d->tok_blob = nullptr;                 // (host-side arrays only, see above)
-    d->elem_poff = reinterpret_cast<const uint32_t*>(base + o_epoff);
+    d->gs_htab = t.gs ? at32(L.gsh) : nullptr;
+    d->gs_hmask = t.gs_hmask;
+    d->gs_rank = t.gs ? at32(L.gsr) : nullptr;
+    d->gs_byte = t.gs ? at32(L.gsb) : nullptr;
+    d->gs_itab = t.gs_in ? at64(L.gsi) : nullptr;
+    d->gs_ilo = t.gs_ilo;
+    d->gs_in = t.gs_in;
+    d->elem_off = at32(L.eoff);
+    d->elem_order = at32(L.eord);
+    d->elem_byte = at(L.eb);
+    d->tok_mask = at64(L.mask);
+    d->tok_off = t.dev_toff ? at32(L.toff) : nullptr;
+    d->tok_order = t.toks ? at(L.tord) : nullptr;
+    d->elem_blob = at(L.eblob);
+    d->tok_blob = nullptr;                 // (host-side arrays only: not kept on the device)
+    d->elem_poff = at32(L.epoff);
     d->tok_poff = nullptr;
-    d->elem_pad = reinterpret_cast<const uint8_t*>(base + o_epad);
-    d->tok_pad = toks ? reinterpret_cast<const uint8_t*>(base + o_tpad) : nullptr;
-    d->tok_desc = toks ? reinterpret_cast<const uint64_t*>(base + o_tdesc) : nullptr;
-    if (tok_headroom && toks && rec_len && hashed) {
+    d->elem_pad = at(L.epad);
+    d->tok_pad = t.toks ? at(L.tpad) : nullptr;
+    d->tok_desc = t.toks ? at64(L.tdesc) : nullptr;
+    if (t.patchable) {
         d->patchable = true;
-        d->h_rank.assign(E, 0);
-        for (uint32_t r = 0; r < E; ++r) d->h_rank[elem_order[r]] = r;
-        d->h_tpoff = std::move(tpoff);         // (~0u marks the empty slots already)
-        d->o_mask = o_mask;
-        d->o_tord = o_tord;
-        d->o_tpad = o_tpad;
-        d->o_tdesc = o_tdesc;
-        d->o_rpad = o_rpad;
-        d->o_rd = o_rd;
-        d->tpad_used = tpad_n - 48;
-        d->tpad_cap = tpad_cap;
+        d->h_rank = std::move(t.h_rank);
+        d->h_tpoff = std::move(t.h_tpoff);     // (~0u marks the empty slots already)
+        d->lay = L;
+        d->tpad_used = t.tpad_used;
+        d->tpad_cap = t.tpad_cap;
     }
     *out = d;
     return LASPJ_OK;
@@ -6089,11 +5706,6 @@ namespace laspj {
 
 namespace {
 
-struct PatchRec {
-    u64 dst;            // byte offset in the dictionary's block
-    uint32_t src, len;  // bytes [src, src + len) of the staged patch data
-};
-
 // one block per record, bytes copied as they stand (records are a few hundred bytes)
 __global__ __launch_bounds__(kBlock) void k_patch(const uint8_t* src, const PatchRec* recs,
                                                   uint32_t n, uint8_t* base) {
@@ -6114,185 +5726,64 @@ int etf_dict_create_ex(laspj_ctx* ctx, uint32_t E, const uint8_t* elem_blob,
 }
 
 // The device rows of element slots `dirty` (each gained tokens in the host dictionary `hd`
-// since `d` was built or last patched) rewritten from the host dictionary, as a full
-// rebuild would write them: token mask, term order, writer descriptors (a new token's
-// padded image appended to the image area), record templates, the from_binary tables of
-// its rank (bucket word and shift chosen again, bucket per term rank, slot -> rank).  One
-// staged copy of the rows and one scatter launch, on the context's stream.  Returns
-// LASPJ_E_UNSUPPORTED (nothing written) when only a rebuild will do: a dictionary built
-// without headroom, an element past its token headroom, a token image of another length,
-// no bucket choice that separates the element's tokens, the image area full.
+// since `d` was built or last patched) rewritten from the host dictionary by the full
+// build's own row writers (dict_patch_rows).  One staged copy of the rows and one scatter
+// launch, on the context's stream.  Returns LASPJ_E_UNSUPPORTED (nothing written) when only
+// a rebuild will do (dict_patch_rows' cases).
 int etf_dict_patch(laspj_ctx* ctx, laspj_etf_dict* d, const laspj_dict* hd,
                    const uint32_t* dirty, uint32_t n) {
-    if (!d || !d->patchable) return LASPJ_E_UNSUPPORTED;
-    if (n == 0) return LASPJ_OK;
-    const uint32_t E = d->elements, RK = d->tok_max, RL = d->rec_len;
-    const uint64_t RS = d->rec_stride;
-    const uint32_t TL = d->tok_uniform;
-    std::vector<uint8_t> data;
-    std::vector<PatchRec> recs;
-    auto put = [&](u64 dst, const void* p, uint32_t len) {
-        const uint32_t at = (uint32_t)data.size();
-        data.resize(data.size() + ((len + 15u) & ~15u), 0);
-        std::memcpy(data.data() + at, p, len);
-        recs.push_back(PatchRec{dst, at, len});
-    };
-    uint64_t tpad_used = d->tpad_used;
-    uint32_t big_add = 0;
-    std::vector<std::pair<uint64_t, uint32_t>> new_tpoff;     // (slot index, offset)
-    std::vector<std::string_view> imgs;
-    std::vector<uint8_t> order;
-    const uint64_t o_desc = d->o_rd, o_tb = d->o_rd + 80ull * E,
-                   o_ros = o_tb + 2ull * E * RK;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t e = dirty[i];
-        if (e >= E || !dict_tokens(hd, e, &imgs, &order)) return LASPJ_E_UNSUPPORTED;
-        const uint32_t cnt = (uint32_t)imgs.size();
-        if (cnt > RK || cnt > 64 || cnt == 0) return LASPJ_E_UNSUPPORTED;
-        {
-            uint32_t had = 0;                  // (the element's count the images hold)
-            for (uint32_t k = 0; k < 64; ++k) had += d->h_tpoff[64ull * e + k] != 0xFFFFFFFFu;
-            if (had <= kSmallTok && cnt > kSmallTok) ++big_add;
-        }
-        for (const auto& im : imgs)
-            if (im.size() != TL || TL + 2u != RL) return LASPJ_E_UNSUPPORTED;
-        for (const auto& im : imgs)
-            if (!tok_is_binary(reinterpret_cast<const uint8_t*>(im.data()), TL)) d->bin_tokens = false;
-        // token mask and term order
-        const u64 mask = cnt == 64 ? ~0ull : (1ull << cnt) - 1ull;
-        put(d->o_mask + 8ull * e, &mask, 8);
-        uint8_t ord[64];
-        std::memset(ord, 0xFF, 64);
-        std::memcpy(ord, order.data(), cnt);
-        put(d->o_tord + 64ull * e, ord, 64);
-        // padded images of the new slots, appended
-        uint32_t tpo[64];
-        for (uint32_t k = 0; k < 64; ++k) {
-            uint32_t o = k < cnt ? d->h_tpoff[64ull * e + k] : 0xFFFFFFFFu;
-            for (const auto& nt : new_tpoff)
-                if (nt.first == 64ull * e + k) o = nt.second;
-            if (k < cnt && o == 0xFFFFFFFFu) {
-                const uint64_t need = (TL + 15u) & ~15u;
-                if (tpad_used + need + 48 > d->tpad_cap) return LASPJ_E_UNSUPPORTED;
-                o = (uint32_t)tpad_used;
-                tpad_used += need;
-                put(d->o_tpad + o, imgs[k].data(), TL);
-                new_tpoff.emplace_back(64ull * e + k, o);
-            }
-            tpo[k] = o;
-        }
-        // writer descriptors by term rank: slot | length << 8 | padded offset << 32
-        u64 td[64];
-        for (uint32_t j = 0; j < RK; ++j)
-            td[j] = j < cnt ? (u64)order[j] | ((u64)TL << 8) | ((u64)tpo[order[j]] << 32) : 0xFFull;
-        put(d->o_tdesc + 8ull * RK * e, td, 8 * RK);
-        // record templates by term rank
-        std::vector<uint8_t> rows((size_t)RK * RS, 0);
-        for (uint32_t j = 0; j < cnt; ++j) {
-            uint8_t* r = rows.data() + j * RS;
-            r[0] = 104;
-            r[1] = 2;
-            std::memcpy(r + 2, imgs[order[j]].data(), TL);
-        }
-        put(d->o_rpad + (u64)e * RK * RS, rows.data(), (uint32_t)rows.size());
-        // from_binary tables of the element's rank
-        const uint32_t r = d->h_rank[e];
-        uint32_t key = 0;
-        std::vector<uint16_t> tb(RK, 0);
-        bool placed = false;
-        std::vector<uint32_t> keys(cnt);
-        for (uint32_t wi = RL / 4; wi-- > 0 && !placed;) {
-            for (uint32_t j = 0; j < cnt; ++j) std::memcpy(&keys[j], rows.data() + j * RS + 4 * wi, 4);
-            for (uint32_t sh = 0; sh + 10 <= 32 && !placed; ++sh) {
-                uint64_t seen[kBuckets / 64] = {};
-                bool ok = true;
-                for (uint32_t j = 0; j < cnt && ok; ++j) {
-                    const uint32_t bk = (keys[j] >> sh) & (kBuckets - 1u);
-                    ok = !((seen[bk / 64] >> (bk % 64)) & 1ull);
-                    seen[bk / 64] |= 1ull << (bk % 64);
-                }
-                if (!ok) continue;
-                placed = true;
-                key = wi | (sh << 8);
-                for (uint32_t j = 0; j < cnt; ++j) tb[j] = (uint16_t)((keys[j] >> sh) & (kBuckets - 1u));
-            }
-        }
-        if (!placed) {
-            key = kNoBuckets;                  // (matched template by template, see create)
-            for (uint32_t j = 0; j < cnt; ++j) tb[j] = 0xFFFFu;
-        }
-        // descriptor {slot, header length, key, tokens}: the first two do not change
-        const uint32_t kc[2] = {key, cnt};
-        put(o_desc + 16ull * r + 8, kc, 8);
-        put(o_tb + 2ull * r * RK, tb.data(), 2 * RK);
-        uint8_t ros[64];
-        std::memset(ros, 0xFF, 64);
-        for (uint32_t j = 0; j < cnt; ++j) ros[order[j]] = (uint8_t)j;
-        put(o_ros + 64ull * r, ros, 64);
-    }
-    // stage and scatter
+    if (!d) return LASPJ_E_UNSUPPORTED;
+    const DictPatchIn in{d->patchable,   d->elements,      d->tok_max,        d->rec_len,
+                         d->rec_stride,  d->tok_uniform,   &d->lay,           d->h_rank.data(),
+                         d->h_tpoff.data(), d->tpad_used,  d->tpad_cap};
+    DictPatch p;
+    const int st = dict_patch_rows(in, hd, dirty, n, &p);
+    if (p.lost_bin) d->bin_tokens = false;
+    if (st != LASPJ_OK || n == 0) return st;
+    // stage and scatter: the rows, then their records
     std::lock_guard<std::mutex> lk(ctx->mu);
     hipSetDevice(ctx->device);
-    const uint64_t rec_bytes = recs.size() * sizeof(PatchRec);
-    const uint64_t total = data.size() + ((rec_bytes + 15) & ~15ull);
+    const uint64_t dlen = p.data.size(), rec_bytes = p.recs.size() * sizeof(PatchRec);
+    const uint64_t total = dlen + ((rec_bytes + 15) & ~15ull);
+    const char* dev = nullptr;
     if (total <= laspj_ctx::kUpSmall) {
         // a few elements' rows (an update's token, a bind's new tokens): through the pinned
         // upload ring, with no wait for the stream's earlier work
-        data.resize(total, 0);
-        std::memcpy(data.data() + (total - ((rec_bytes + 15) & ~15ull)), recs.data(), rec_bytes);
-        const uint64_t dlen = total - ((rec_bytes + 15) & ~15ull);
-        const void* staged = stage_small(ctx, data.data(), total);
-        if (staged) {
+        p.data.resize(total, 0);
+        std::memcpy(p.data.data() + dlen, p.recs.data(), rec_bytes);
+        if (const void* staged = stage_small(ctx, p.data.data(), total)) {
             // k_patch reads the staged rows in place from pinned memory (a few KB: no copy
             // to launch first)
-            const char* dev = static_cast<const char*>(staged_dev(ctx, staged));
+            dev = static_cast<const char*>(staged_dev(ctx, staged));
             if (!dev) {
                 if (int s = reserve_scratch(ctx, total)) return s;
-                char* sc = static_cast<char*>(ctx->scratch);
-                if (hipMemcpyAsync(sc, staged, total, hipMemcpyHostToDevice, ctx->stream) !=
-                    hipSuccess)
+                if (hipMemcpyAsync(ctx->scratch, staged, total, hipMemcpyHostToDevice,
+                                   ctx->stream) != hipSuccess)
                     return LASPJ_E_DEVICE;
-                dev = sc;
+                dev = static_cast<const char*>(ctx->scratch);
             }
-            hipLaunchKernelGGL(k_patch, dim3((unsigned)std::min<uint64_t>(recs.size(), 4096)),
-                               dim3(kBlock), 0, ctx->stream, reinterpret_cast<const uint8_t*>(dev),
-                               reinterpret_cast<const PatchRec*>(dev + dlen),
-                               (uint32_t)recs.size(), static_cast<uint8_t*>(d->block));
-            if (hipGetLastError() != hipSuccess) return LASPJ_E_DEVICE;
-            for (const auto& nt : new_tpoff) d->h_tpoff[nt.first] = nt.second;
-            d->tpad_used = tpad_used;
-            d->big_elems += big_add;
-            return LASPJ_OK;
         }
-        data.resize(dlen);
     }
-    hipStreamSynchronize(ctx->stream);                // the pinned staging is free
-    if (ctx->dstage_bytes < total) {
-        if (ctx->dstage) hipHostFree(ctx->dstage);
-        ctx->dstage = nullptr;
-        ctx->dstage_bytes = 0;
-        if (hipHostMalloc(&ctx->dstage, std::max<uint64_t>(total, 1ull << 20), hipHostMallocDefault) != hipSuccess) {
-            hipGetLastError();
-            ctx->dstage = nullptr;
-            return LASPJ_E_NOMEM;
-        }
-        ctx->dstage_bytes = std::max<uint64_t>(total, 1ull << 20);
+    if (!dev) {
+        hipStreamSynchronize(ctx->stream);                // the pinned staging is free
+        if (!grow_dstage(ctx, total, std::max<uint64_t>(total, 1ull << 20))) return LASPJ_E_NOMEM;
+        char* st = static_cast<char*>(ctx->dstage);
+        std::memcpy(st, p.data.data(), dlen);
+        std::memcpy(st + dlen, p.recs.data(), rec_bytes);
+        if (int s = reserve_scratch(ctx, total)) return s;
+        if (hipMemcpyAsync(ctx->scratch, st, total, hipMemcpyHostToDevice, ctx->stream) !=
+            hipSuccess)
+            return LASPJ_E_DEVICE;
+        dev = static_cast<const char*>(ctx->scratch);
     }
-    char* st = static_cast<char*>(ctx->dstage);
-    std::memcpy(st, data.data(), data.size());
-    std::memcpy(st + data.size(), recs.data(), rec_bytes);
-    if (int s = reserve_scratch(ctx, total)) return s;
-    char* dev = static_cast<char*>(ctx->scratch);
-    if (hipMemcpyAsync(dev, st, total, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return LASPJ_E_DEVICE;
-    hipLaunchKernelGGL(k_patch, dim3((unsigned)std::min<uint64_t>(recs.size(), 4096)), dim3(kBlock),
-                       0, ctx->stream, reinterpret_cast<const uint8_t*>(dev),
-                       reinterpret_cast<const PatchRec*>(dev + data.size()), (uint32_t)recs.size(),
+    hipLaunchKernelGGL(k_patch, dim3((unsigned)std::min<uint64_t>(p.recs.size(), 4096)),
+                       dim3(kBlock), 0, ctx->stream, reinterpret_cast<const uint8_t*>(dev),
+                       reinterpret_cast<const PatchRec*>(dev + dlen), (uint32_t)p.recs.size(),
                        static_cast<uint8_t*>(d->block));
     if (hipGetLastError() != hipSuccess) return LASPJ_E_DEVICE;
-    for (const auto& nt : new_tpoff) d->h_tpoff[nt.first] = nt.second;
-    d->tpad_used = tpad_used;
-    d->big_elems += big_add;
+    for (const auto& nt : p.new_tpoff) d->h_tpoff[nt.first] = nt.second;
+    d->tpad_used = p.tpad_used;
+    d->big_elems += p.big_add;
     return LASPJ_OK;
 }
 

@@ -988,7 +988,7 @@ int laspj_dict_export(const laspj_dict* dict, uint32_t E, uint8_t* elem_blob, ui
                                 return cmp_view(d.toks[e][x], d.toks[e][y]) < 0;
                             });
                         }
-                        memcpy(o, ts.data(), ts.size());
+                        if (!ts.empty()) memcpy(o, ts.data(), ts.size());
                     }
                 }
             }
