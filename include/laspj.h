@@ -1446,6 +1446,64 @@ int laspj_map_args(laspj_map* m, const uint8_t** out, uint64_t* out_len,
  * A fun that raised never gets here: the process crashes, as the reference's does. */
 int laspj_map_results(laspj_map* m, const uint8_t* results, uint64_t n, int32_t* verdict);
 
+/* ----------------------------------------------------------------- resident fold processes */
+/* lasp_process:process/3 (lasp_process.erl:61-95) re-runs fold/6's body (lasp_core.erl:460-486)
+ * whenever its input changes: AccValue = lists:foldl(fun({X, C}, Acc) -> Acc ++ [{V, C} || V <-
+ * Function(X)] end, [], Value), bound with bind/3 (:291-312) — the reference's flat-map, the
+ * one body whose output can hold more entries than its input and repeats keys by design
+ * (riak_test/lasp_fold_test.erl:59-87).  It is the map process with a run of outputs per
+ * element: F's result lists are kept beside the input's namespace as a pool of rows, one per
+ * V in the order slots were evaluated — the element slot V took (`ykey`) and, per token of X,
+ * the slot the token's image holds under V (`tmap`) — and per element slot whether F has been
+ * asked (`evaluated`), where its run of rows lies (`frow`) and which of its tokens every row
+ * maps (`fmapped`).  Every V is registered as the walker of an image registers it
+ * (laspj_lvar_etf_bind), so a produced list and a peer's image of the same value agree id for
+ * id.  The NIF's loop is the map's: run; while pending > 0: args -> F on each -> results ->
+ * run; after a WRITTEN answer laspj_lvar_recheck(out).  Where a clause below does not say
+ * otherwise the contract is laspj_map_*'s, clause for clause; the tables follow the namespace
+ * as the map's do (growth, dictionary reset, wide namespace). */
+typedef struct laspj_fold laspj_fold;
+/* One lasp_process running fold/6 (lasp_core.erl:460-486) from the resident OR-Set in into the
+ * list-valued variable out of the same context and namespace.  Kind and namespace checks as
+ * laspj_map_create: in not an OR-Set: LASPJ_E_KIND; two namespaces: LASPJ_E_UNSUPPORTED — the
+ * NIF keeps the image path, laspj_list_etf_fold, for that process; null arguments:
+ * LASPJ_E_INVAL.  Several folds and maps may share one in.  Destroying in, out or the context
+ * kills the fold: its later calls answer LASPJ_E_INVAL (laspj_fold_destroy still frees it). */
+int laspj_fold_create(laspj_var* in, laspj_lvar* out, laspj_fold** f);
+/* the process ends (lasp_process.erl:61-95 terminates): its tables are released (the terms it
+ * registered stay in the namespace, as a walked image's do) */
+int laspj_fold_destroy(laspj_fold* f);
+/* One re-run of fold/6's body plus bind/3 (lasp_core.erl:460-486, 291-312).  *pending = the
+ * element slots in holds (any token, tombstoned ones too) that F has not been asked about.
+ * *pending > 0: out is untouched, *status LASPJ_BIND_NOOP.  *pending == 0: AccValue holds, for
+ * each held slot in the term order of the input's keys and for each V of F(X) in F's own list
+ * order, duplicates kept, the entry {V, Cx} with Cx's tokens in term order and their removed
+ * flags; it is bound into out as laspj_lvar_intersection binds: *status LASPJ_BIND_NOOP,
+ * LASPJ_BIND_WRITTEN or LASPJ_BIND_REFUSED.  Tokens minted on known elements since the last
+ * run need no fun.  One synchronisation in steady state; the waiters of out are not re-checked
+ * (laspj_lvar_recheck after WRITTEN).  verdict FALLBACK, out exactly as it was: in is not a
+ * current resident OR-Set value, the namespace is wide, out is held on the host, or the fold
+ * is refused (laspj_fold_results).  LASPJ_E_RANGE: AccValue would pass 2^32 - 16 entries or
+ * tokens. */
+int laspj_fold_run(laspj_fold* f, int32_t* status, uint32_t* pending, int32_t* verdict);
+/* The arguments fold/6's body would call Function on and the device has no result for
+ * (lasp_core.erl:470-476): as laspj_map_args — term_to_binary/1 of their list in term order;
+ * nothing is registered; *out is valid until the context's next call. */
+int laspj_fold_args(laspj_fold* f, const uint8_t** out, uint64_t* out_len,
+                    uint32_t* count, int32_t* verdict);
+/* Function's results for laspj_fold_args' list, in its order (lasp_core.erl:470-476):
+ * term_to_binary/1 of the list of F(X), each itself a proper list, possibly [].  Under one
+ * dictionary journal every V is registered as an element of the input's namespace and every
+ * token X has registered as a token of V (tokens the fold itself put under a key that is also
+ * an input are not passed on, as the map's).  verdict FALLBACK — the journal rolled back,
+ * nothing recorded, the fold refused until the next dictionary reset (variables, filters, maps
+ * and other folds of the namespace carry on): a V `==` to a registered term under another
+ * image, a V of a term kind the dictionary does not hold, or a key that would pass 64 tokens.
+ * LASPJ_E_INVAL with nothing recorded: a length other than the list's, no list outstanding, or
+ * an F(X) that is not a proper list (the comprehension of :470 raises bad_generator); after a
+ * dictionary reset dropped the list: LASPJ_OK with nothing recorded. */
+int laspj_fold_results(laspj_fold* f, const uint8_t* results, uint64_t n, int32_t* verdict);
+
 /* ------------------------------------------------------------------ timing */
 int laspj_event_create(laspj_ctx* ctx, laspj_event** out);
 int laspj_event_destroy(laspj_event* ev);

@@ -282,6 +282,11 @@ SIGNATURES = {
     "laspj_map_run": (i, [vp, C.POINTER(C.c_int32), C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_map_args": (i, [vp, vpp, C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_map_results": (i, [vp, vp, u64, C.POINTER(C.c_int32)]),
+    "laspj_fold_create": (i, [vp, vp, vpp]),
+    "laspj_fold_destroy": (i, [vp]),
+    "laspj_fold_run": (i, [vp, C.POINTER(C.c_int32), C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_fold_args": (i, [vp, vpp, C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_fold_results": (i, [vp, vp, u64, C.POINTER(C.c_int32)]),
     "laspj_var_etf_update": (i, [vp, vp, u64, C.POINTER(C.c_int32), vpp, C.POINTER(u64), vpp,
                                  C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_var_etf_increment": (i, [vp, vp, u64, vp, u64, vp, u32, C.POINTER(u32),

@@ -18,7 +18,7 @@ SOURCES = ["laspj_runtime.hip", "laspj_kernels.hip", "laspj_combinators.hip",
            "laspj_codec.hip", "laspj_lists.hip", "laspj_comm.hip",
            "laspj_many.hip", "laspj_wide.hip", "laspj_nif.hip", "laspj_nif_vars.hip",
            "laspj_nif_waiters.hip", "laspj_nif_process.hip", "laspj_nif_lvars.hip",
-           "laspj_nif_maps.hip", "laspj_host.cpp", "laspj_list_etf.cpp",
+           "laspj_nif_maps.hip", "laspj_nif_folds.hip", "laspj_host.cpp", "laspj_list_etf.cpp",
            "laspj_counters.hip", "laspj_counter_host.cpp", "laspj_process.hip",
            "laspj_reads.hip", "laspj_reads_host.cpp", "laspj_lvars.hip",
            "laspj_dict_tables.cpp"]

@@ -775,6 +775,32 @@ struct LmMap {
 // rec again.  No synchronisation.
 hipError_t launch_lm_map(laspj_ctx* ctx, const LmMap& a, const ListDev& out, uint64_t* tiles,
                          uint32_t* rec, uint32_t* ans, bool count_only);
+// fold/6's body (lasp_core.erl:460-486) from one variable's cells and a fold process's tables
+// (include/laspj.h "resident fold processes"): per term-order position j < n, e =
+// elem_order[j]; a held cell of an evaluated slot whose present tokens are all in fmapped[e]
+// emits frow[e].count entries — row r = first + i gives {ykey[r], its tokens through tmap[r]},
+// placed by that key's rank row.  Pending and unmapped as the map's; a slot with no rows
+// emits nothing.  The slot tables cover E slots, the row tables `rows` rows.
+struct LfFold {
+    const uint64_t* in;
+    uint32_t Ein;
+    uint32_t n;
+    const uint32_t* elem_order;
+    const uint32_t* grank;              // 64 words per element slot
+    const uint64_t* evaluated;          // `words` words
+    uint64_t* pmask;                    // `words` words: the pass's pending slots
+    const uint64_t* frow;               // E words: first row | row count << 32
+    const uint64_t* fmapped;            // E words: the token slots mapped in every row
+    const uint32_t* ykey;               // `rows` words: the element slot V took
+    const uint8_t* tmap;                // 64 `rows` bytes
+    uint32_t E, words, rows;
+};
+// As launch_lm_map; ans = {entries, tokens, overflow, pending, unmapped, fault}: the caller
+// zeroes ans[5], and a writer that finds the row tables at odds with frow / fmapped (a row
+// past `rows`, a key past E, a tmap byte of a promised token that names no slot or one taken
+// already) writes in-range items and sets it.
+hipError_t launch_lf_fold(laspj_ctx* ctx, const LfFold& a, const ListDev& out, uint64_t* tiles,
+                          uint32_t* rec, uint32_t* ans, bool count_only);
 
 // the host's half (laspj_reads_host.cpp: no device, no lock)
 // wave items of a read whose longest block of cells has `words` u64 words

@@ -22,7 +22,9 @@
 // ordered by the stream.  Every write is checked against the output's capacity.
 //
 // map/6 (lasp_core.erl:641-667; include/laspj.h "resident map processes") is the same producer
-// over one variable's cells and a map process's tables: k_lm_count / k_lm_write below.
+// over one variable's cells and a map process's tables: k_lm_count / k_lm_write below; fold/6
+// (lasp_core.erl:460-486; "resident fold processes") emits a run of entries per cell:
+// k_lf_count / k_lf_write.
 
 #include "laspj_internal.h"
 
@@ -342,6 +344,175 @@ __global__ __launch_bounds__(kLvT) void k_lm_write(LmMap a, ListDev out, const u
     }
 }
 
+// ---- fold/6 (lasp_core.erl:460-486) from a variable's cells and a fold process's tables ----
+// AccValue = foldl(fun({X, C}, Acc) -> Acc ++ [{V, C} || V <- F(X)] end, [], Value): a held
+// slot e emits one entry per row of its run frow[e] = {first, count} of the row pool, row r
+// keyed ykey[r] with the cell's tokens named through tmap[r] in that key's rank row.  The
+// count is O(1) per position (fmapped[e] says which token slots every row of e maps); the
+// writer spreads a tile's output entries, not its positions, over the block.
+
+// what slot e's cell gives: its entries and tokens; un: present tokens outside fmapped (the
+// cell then emits nothing, as does a held slot F has not been asked about)
+struct LfPos {
+    Cnt c;
+    uint32_t un;
+};
+
+__device__ __forceinline__ LfPos lf_pos(const LfFold& a, uint32_t e) {
+    LfPos o{Cnt{0, 0}, 0};
+    if (e >= a.Ein || e >= a.E) return o;
+    const u64x2 C = *reinterpret_cast<const u64x2*>(a.in + 2ull * e);
+    if (!C.x || !((a.evaluated[e >> 6] >> (e & 63u)) & 1ull)) return o;
+    const uint32_t cnt = (uint32_t)(a.frow[e] >> 32);
+    if (!cnt) return o;                                    // F(X) = []
+    const u64 miss = C.x & ~a.fmapped[e];
+    if (miss) {
+        o.un = (uint32_t)__popcll(miss);
+        return o;
+    }
+    o.c = Cnt{cnt, cnt * (uint32_t)__popcll(C.x)};
+    return o;
+}
+
+__global__ __launch_bounds__(kLvT) void k_lf_count(LfFold a, u64* tiles, uint32_t* rec) {
+    __shared__ Cnt lds[kLvT / 64];
+    const uint32_t lane = threadIdx.x & 63u;
+    // the pending check over this tile's element slots in slot order, as k_lm_count's
+    {
+        const uint32_t w0 = (blockIdx.x * kLvTile + (threadIdx.x & ~63u) * kLvI) >> 6;
+        uint32_t pend = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kLvI; ++i) {
+            const uint32_t w = w0 + i, s = 64u * w + lane;
+            if (w >= a.words) break;                       // (wave-uniform)
+            const bool held = s < a.Ein && a.in[2ull * s] != 0;
+            const u64 pm = __ballot(held) & ~a.evaluated[w];
+            if (lane == 0) a.pmask[w] = pm;
+            pend += (uint32_t)__popcll(pm);
+        }
+        if (lane == 0 && pend) lm_rec_add(rec, pend);
+    }
+    const uint32_t j0 = blockIdx.x * kLvTile + threadIdx.x * kLvI;
+    uint32_t e[kLvI];
+    lv_slots(a, j0, e);
+    Cnt mine{0, 0};
+    uint32_t un = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        const LfPos c = lf_pos(a, e[k]);
+        mine.e += c.c.e;
+        mine.t += c.c.t;
+        un += c.un;
+    }
+    if (__ballot(un != 0)) {                               // (rare: a token minted since)
+        for (int s = 32; s; s >>= 1) un += __shfl_xor(un, s, 64);
+        if (lane == 0) lm_rec_add(rec + 1, un);
+    }
+    Cnt tot;
+    lv_block_excl(mine, lds, &tot);
+    if (threadIdx.x == 0) {
+        tiles[2ull * blockIdx.x] = tot.e;
+        tiles[2ull * blockIdx.x + 1] = tot.t;
+    }
+}
+
+__global__ __launch_bounds__(kLvT) void k_lf_write(LfFold a, ListDev out, const u64* tiles,
+                                                   uint32_t* rec, uint32_t* ans) {
+    __shared__ Cnt lds[kLvT / 64];
+    __shared__ uint32_t off_e[kLvTile], off_t[kLvTile];   // each position's exclusive offsets
+    Cnt pre{0, 0};
+    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += kLvT) {
+        pre.e += (uint32_t)tiles[2ull * i];
+        pre.t += (uint32_t)tiles[2ull * i + 1];
+    }
+    Cnt base;
+    lv_block_excl(pre, lds, &base);
+    const uint32_t j0 = blockIdx.x * kLvTile + threadIdx.x * kLvI;
+    Cnt tot;
+    {
+        uint32_t e[kLvI];
+        lv_slots(a, j0, e);
+        Cnt c[kLvI], mine{0, 0};
+#pragma unroll
+        for (uint32_t k = 0; k < kLvI; ++k) {
+            c[k] = lf_pos(a, e[k]).c;
+            mine.e += c[k].e;
+            mine.t += c[k].t;
+        }
+        Cnt ex = lv_block_excl(mine, lds, &tot);
+#pragma unroll
+        for (uint32_t k = 0; k < kLvI; ++k) {
+            off_e[threadIdx.x * kLvI + k] = ex.e;
+            off_t[threadIdx.x * kLvI + k] = ex.t;
+            ex.e += c[k].e;
+            ex.t += c[k].t;
+        }
+    }
+    __syncthreads();
+    // the tile's output entries over the block: entry i belongs to the last position whose
+    // offset is <= i (one that emits: the positions without output share the next one's)
+    for (uint32_t i = threadIdx.x; i < tot.e; i += kLvT) {
+        uint32_t lo = 0, hi = kLvTile - 1;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (off_e[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        const uint32_t j = blockIdx.x * kLvTile + lo;
+        if (j >= a.n) continue;                            // (never: such a position emits nothing)
+        const uint32_t e = a.elem_order[j];
+        if (e >= a.Ein || e >= a.E) continue;              // (likewise)
+        const u64x2 C = *reinterpret_cast<const u64x2*>(a.in + 2ull * e);
+        const uint32_t pc = (uint32_t)__popcll(C.x), d = i - off_e[lo];
+        const uint32_t pos = base.e + i;
+        const u64 tp = (u64)base.t + off_t[lo] + (u64)d * pc;
+        if (pos >= out.ce || tp + pc > out.ct) continue;
+        const u64 row = (u64)(uint32_t)a.frow[e] + d;
+        // whatever the row tables hold, the items name a slot below E and a token below 64
+        bool bad = row >= a.rows;
+        uint32_t y = bad ? e : a.ykey[row];
+        if (y >= a.E) {
+            bad = true;
+            y = e;
+        }
+        u64 q = 0, qr = 0;
+        if (!bad) {
+            const uint8_t* tm = a.tmap + 64ull * row;
+            for (u64 b = C.x; b; b &= b - 1) {
+                const uint32_t k = (uint32_t)__builtin_ctzll(b), k2 = tm[k];
+                if (k2 >= 64u || ((q >> k2) & 1ull)) {     // fmapped promised a slot of its own
+                    bad = true;
+                    break;
+                }
+                q |= 1ull << k2;
+                qr |= ((C.y >> k) & 1ull) << k2;
+            }
+        }
+        out.key[pos] = y;
+        out.toff[pos] = (uint32_t)tp;
+        if (bad) {
+            ans[5] = 1;
+            for (uint32_t t = 0; t < pc; ++t) out.tok[tp + t] = 64ull * y + t;
+        } else {
+            lv_run(out.tok + tp, y, q, qr, a.grank + 64ull * y);
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        const uint32_t ne = base.e + tot.e, nt = base.t + tot.t;
+        const bool over = ne > out.ce || nt > out.ct;
+        out.hdr[0] = over ? 0u : ne;
+        out.hdr[1] = over ? 0u : nt;
+        out.toff[over ? 0u : ne] = over ? 0u : nt;
+        ans[0] = ne;
+        ans[1] = nt;
+        ans[2] = over ? 1u : 0u;
+        ans[3] = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ans[4] = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rec[0] = 0;
+        rec[1] = 0;
+    }
+}
+
 // one wave per element slot: lane j reads the slot of term-order place j of its tokens
 __global__ __launch_bounds__(256) void k_lv_ranks(const uint32_t* __restrict__ elem_order,
                                                   const uint8_t* __restrict__ tok_order, uint32_t E,
@@ -388,6 +559,16 @@ hipError_t launch_lm_map(laspj_ctx* ctx, const LmMap& a, const ListDev& out, uin
     hipLaunchKernelGGL(k_lm_count, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, tiles, rec);
     if (!count_only)
         hipLaunchKernelGGL(k_lm_write, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, out, tiles, rec,
+                           ans);
+    return hipGetLastError();
+}
+
+hipError_t launch_lf_fold(laspj_ctx* ctx, const LfFold& a, const ListDev& out, uint64_t* tiles,
+                          uint32_t* rec, uint32_t* ans, bool count_only) {
+    const uint32_t ntile = lv_isect_tiles(a.n);
+    hipLaunchKernelGGL(k_lf_count, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, tiles, rec);
+    if (!count_only)
+        hipLaunchKernelGGL(k_lf_write, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, out, tiles, rec,
                            ans);
     return hipGetLastError();
 }

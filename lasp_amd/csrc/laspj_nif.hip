@@ -325,6 +325,7 @@ int rebuild_etf(laspj_ctx* ctx, NifState* S, KindState& K) {
     K.rank_full = true;                             // (the order tables follow the images)
     K.rank_dirty.clear();
     for (laspj_map* m : K.maps) m->tok_all = true;  // (any element may have gained tokens)
+    for (laspj_fold* f : K.folds) f->tok_all = true;
     ++S->stats[ST_REBUILDS];
     S->stats[ST_NS_IMAGES] += now_ns() - t0;
     return LASPJ_OK;
@@ -356,6 +357,8 @@ bool patch_etf(laspj_ctx* ctx, NifState* S, KindState& K) {
         K.rank_dirty.insert(K.rank_dirty.end(), dirty.begin(), dirty.end());
     for (laspj_map* m : K.maps)
         if (!m->tok_all) m->tok_dirty.insert(m->tok_dirty.end(), dirty.begin(), dirty.end());
+    for (laspj_fold* f : K.folds)
+        if (!f->tok_all) f->tok_dirty.insert(f->tok_dirty.end(), dirty.begin(), dirty.end());
     K.stale = false;
     ++S->stats[ST_PATCHES];
     S->stats[ST_NS_IMAGES] += now_ns() - t0;
@@ -1625,6 +1628,7 @@ void nif_destroy(laspj_ctx* ctx) {
             }
             S->filters.clear();
             maps_ctx_gone(ctx, S);
+            folds_ctx_gone(ctx, S);
         }
         // the list-valued variables' lists go with the context; one outliving it is dead
         for (laspj_lvar* lv : S->lvars) {

@@ -21,6 +21,7 @@
 #include "laspj_internal.h"
 
 struct laspj_map;
+struct laspj_fold;
 
 namespace laspj {
 
@@ -73,6 +74,8 @@ struct KindState {
     // rewrote — elements that gained tokens, which the map then names under its keys before
     // its next pass — and rebuild_etf says "all"
     std::unordered_set<laspj_map*> maps;
+    // the fold processes (laspj_fold), handed the same slots
+    std::unordered_set<laspj_fold*> folds;
 };
 
 // One entry of `#dv.waiting_threads` ({threshold, read, From, Type, Threshold},
@@ -213,6 +216,53 @@ struct laspj_map {
     std::string image;
 };
 
+// One lasp_process running fold/6 (lasp_core.erl:460-486) from the OR-Set `in` into the list
+// variable `out` (include/laspj.h "resident fold processes").  F(X) is a list, so a slot owns
+// a run of rows of a pool appended in the order slots are evaluated: per element slot e
+// whether F has been asked (evaluated), its run (frow: first row | count << 32) and the token
+// slots mapped in every row of the run (fmapped); per row the element slot V took (ykey) and,
+// per token slot k of e, the slot the token's image holds under that key (tmap, 0xFF: not
+// mapped).  On the device (dev: [rec {pending, unmapped} | evaluated | pmask | frow | fmapped
+// | ykey | tmap], over E slots and row_cap rows) with all but pmask mirrored on the host;
+// what changed is uploaded ahead of the next pass.
+struct laspj_fold {
+    laspj_ctx* ctx = nullptr;        // null once the context is gone
+    laspj_var* in = nullptr;         // null once in or out is destroyed: the fold is dead
+    laspj_lvar* out = nullptr;       // and its calls answer LASPJ_E_INVAL
+    std::shared_ptr<laspj::KindState> ns;
+    uint64_t epoch = 0;              // the dictionary generation the tables refer to
+    uint32_t E = 0, words = 0;       // the slots the device tables cover
+    uint32_t row_cap = 0;            // the rows the device pool has room for
+    uint32_t rows_up = 0;            // the rows the device pool has got
+    uint8_t* dev = nullptr;
+    uint64_t dev_bytes = 0;
+    std::vector<uint64_t> h_eval;
+    std::vector<uint64_t> h_frow, h_fmapped;     // per slot
+    std::vector<uint32_t> h_ykey;                // per row
+    std::vector<uint8_t> h_tmap;                 // 64 per row
+    // per slot, as the map's: the token slots this fold's own registrations created under it
+    // and how many of its tokens have been looked at
+    std::vector<uint64_t> h_mine;
+    std::vector<uint8_t> h_seen;
+    // sum over slots of rows x tokens looked at: the bound of a pass's tokens
+    uint64_t sum_rt = 0;
+    // mirror entries the device has not got yet: the slots whose evaluated bit / frow changed
+    // (as a range), the slots whose fmapped word and the old rows whose tmap row changed
+    uint32_t up_lo = ~0u, up_hi = 0;
+    std::vector<uint32_t> up_slots, up_rows;
+    bool pmask_valid = false;        // pmask is a pass's of this generation and size
+    bool rec_dirty = true;           // rec is not known zero (a pass without its writer)
+    bool refused = false;            // until the next dictionary reset: FALLBACK
+    bool val_not_asc = false;        // the produced list's keys do not ascend (F's order)
+    // the element slots whose tokens grew since the last look (patch_etf), or all of them
+    std::vector<uint32_t> tok_dirty;
+    bool tok_all = true;
+    // laspj_fold_args' list, as the filter's
+    std::vector<uint32_t> listed;
+    bool outstanding = false, dropped = false;
+    std::string image;
+};
+
 namespace laspj {
 
 // a pinned host block a group-commit waiter stages its payload into while it waits
@@ -327,6 +377,7 @@ struct NifState {
     uint32_t* lv_ans = nullptr;
     uint32_t* lv_ans_d = nullptr;
     std::unordered_set<laspj_map*> maps;         // the live map processes
+    std::unordered_set<laspj_fold*> folds;       // the live fold processes
 };
 
 enum class Op { MERGE, VALUE, EQUAL, INFLATION, BIND, WRITE, THRESHOLD, READ, VVALUE };
@@ -530,6 +581,12 @@ void proc_args_image(const KindState& K, const std::vector<uint64_t>& pm,
 void maps_var_gone(NifState* S, laspj_var* v);
 void maps_lvar_gone(NifState* S, laspj_lvar* lv);
 void maps_ctx_gone(laspj_ctx* ctx, NifState* S);
+
+// ---- laspj_nif_folds.hip ----------------------------------------------------------------
+// the same for the folds
+void folds_var_gone(NifState* S, laspj_var* v);
+void folds_lvar_gone(NifState* S, laspj_lvar* lv);
+void folds_ctx_gone(laspj_ctx* ctx, NifState* S);
 
 // ---- what the entry points open and close with ------------------------------------------
 // An entry point's opening: the handle's context state, the null-argument check, the call

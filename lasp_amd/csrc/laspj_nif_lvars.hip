@@ -481,6 +481,7 @@ int laspj_lvar_destroy(laspj_lvar* lv) {
             S->lvars.erase(lv);
             lv->ns->lvars.erase(lv);
             laspj::maps_lvar_gone(S, lv);        // a map writing into it is dead from here on
+            laspj::folds_lvar_gone(S, lv);       // a fold, likewise
             lvar_free_batches(lv);
             // the namespace's last holder: its dictionary, device images and tables go too
             if (lv->ns.use_count() == 1) laspj::free_ns(*lv->ns);

@@ -555,6 +555,7 @@ int laspj_var_destroy(laspj_var* v) {
                         f->ns.reset();
                     }
                 laspj::maps_var_gone(S, v);              // a map reading it, likewise
+                laspj::folds_var_gone(S, v);
             }
             // the namespace's last variable: its device images go too
             if (v->ns.use_count() == 1) laspj::free_ns(*v->ns);

@@ -246,6 +246,11 @@ class Context:
         into the list variable out_lvar (one namespace)."""
         return NifMap(self, in_var, out_lvar)
 
+    def fold(self, in_var: "NifVar", out_lvar: "NifListVar") -> "NifFold":
+        """laspj_fold_create: a resident lasp_process running fold/6 from the OR-Set in_var
+        into the list variable out_lvar (one namespace)."""
+        return NifFold(self, in_var, out_lvar)
+
     def filter_run_many(self, filters):
         """laspj_filter_run_many: one re-run of each filter in one device pass —
         [(verdict, status, pending)] per filter."""
@@ -773,6 +778,70 @@ class NifMap:
     def close(self):
         if self.h:
             self.L.laspj_map_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NifFold:
+    """laspj_fold: a resident lasp_process running fold/6 (laspj.h "resident fold
+    processes") from a NifVar into a NifListVar; the fun answers a list per element.
+    Shaped as NifMap."""
+
+    def __init__(self, ctx: Context, in_var: NifVar, out_lvar: NifListVar):
+        self.ctx, self.L = ctx, ctx.L
+        self.in_var, self.out_lvar = in_var, out_lvar
+        self.h = C.c_void_p()
+        check(self.L.laspj_fold_create(in_var.h, out_lvar.h, C.byref(self.h)), ctx.h)
+
+    def run(self):
+        """laspj_fold_run: (verdict, status, pending) — pending > 0: out is untouched, go
+        through args / results and run again; else status 0 no-op, 1 written, 2 refused."""
+        st, pend, verd = C.c_int32(), C.c_uint32(), C.c_int32()
+        check(self.L.laspj_fold_run(self.h, C.byref(st), C.byref(pend), C.byref(verd)),
+              self.ctx.h)
+        return int(verd.value), int(st.value), int(pend.value)
+
+    def args(self):
+        """laspj_fold_args: (verdict, image of the pending arguments' list, count)."""
+        out, olen, cnt, verd = C.c_void_p(), C.c_uint64(), C.c_uint32(), C.c_int32()
+        check(self.L.laspj_fold_args(self.h, C.byref(out), C.byref(olen), C.byref(cnt),
+                                     C.byref(verd)), self.ctx.h)
+        if verd.value != 0:
+            return int(verd.value), None, 0
+        return 0, C.string_at(out, olen.value), int(cnt.value)
+
+    def results(self, image: bytes) -> int:
+        """laspj_fold_results: the image of the list of F(X), each a list, for the last args
+        list — the verdict (NIF_FALLBACK: the fold is refused, nothing recorded)."""
+        image = bytes(image)
+        verd = C.c_int32()
+        check(self.L.laspj_fold_results(self.h, image, len(image), C.byref(verd)), self.ctx.h)
+        return int(verd.value)
+
+    def step(self, fun, max_rounds: int = 8):
+        """NifMap.step with a list-valued fun: (verdict, status, pending) of the last run."""
+        from . import etf
+        for _ in range(max_rounds):
+            verd, st, pend = self.run()
+            if verd != 0 or pend == 0:
+                return verd, st, pend
+            verd, img, _n = self.args()
+            if verd != 0:
+                return verd, 0, pend
+            res = [fun(a) for a in etf.binary_to_term(img)]
+            verd = self.results(etf.term_to_binary(res))
+            if verd != 0:
+                return verd, 0, pend
+        raise RuntimeError("NifFold.step: elements still pending")
+
+    def close(self):
+        if self.h:
+            self.L.laspj_fold_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
