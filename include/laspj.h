@@ -1084,8 +1084,11 @@ int laspj_var_intersection(laspj_var* out, laspj_var* l, laspj_var* r,
                            int32_t* status, int32_t* verdict);
 /* lasp_core:update/4 (lasp_core.erl:283-287) on the variable: {ok, Value} =
  * Type:update(Op, Actor, Value0) (lasp_orset.erl:99-117, 222-262; lasp_gset.erl:84-88)
- * applied to the resident cells, then bind/3 of Value, which a successful update always
- * inflates — the variable := Value.  op: term_to_binary/1 of Op — OR-Sets {add, E},
+ * applied to the resident cells, then bind/3 of Value (:291-312) — the variable :=
+ * Type:merge(Value0, Value).  lasp_orset:merge/2 ORs the removed flags of a token both hold
+ * (lasp_orset.erl:128-136): an add by a token Value0 holds removed leaves it removed (Value
+ * alone would say `false`), and the variable's value never goes backwards.  op:
+ * term_to_binary/1 of Op — OR-Sets {add, E},
  * {add_by_token, T, E}, {add_all, Es}, {remove, E}, {remove_all, Es}, {update, Ops};
  * G-Sets {add, E}, {add_all, Es}.  Actor is not an argument: neither type's update reads it
  * (unique/1 ignores it, lasp_orset.erl:261-262).  {add, E} / {add_all, Es} mint each
@@ -1102,8 +1105,8 @@ int laspj_var_intersection(laspj_var* out, laspj_var* l, laspj_var* r,
  * verdict FALLBACK: an Op no clause of the reference's update/3 takes as written (it
  * raises), a term `==` to one the namespace holds under another image, a token of another
  * image length in a wide namespace, a host-held variable — the NIF runs the reference's
- * update on the read value and writes the result (an element's 65th token widens the
- * namespace instead).  A counter (lasp_core.erl:283-287: riak_dt_gcounter:update/3 reads
+ * update on the read value and writes its merge with that value (an element's 65th token
+ * widens the namespace instead).  A counter (lasp_core.erl:283-287: riak_dt_gcounter:update/3 reads
  * its Actor): FALLBACK; laspj_var_etf_increment takes the Actor. */
 #define LASPJ_UPDATE_OK          0
 #define LASPJ_UPDATE_NOT_PRESENT 1

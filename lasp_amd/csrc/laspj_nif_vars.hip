@@ -1,5 +1,5 @@
 // Device-resident variables (include/laspj.h "resident variables"): their lifecycle,
-// the group-commit bind queue, write / read / value / threshold, union/7 and update/3 with
+// the group-commit bind queue, write / read / value / threshold, union/7 and update/4 with
 // their kernels.  The passes themselves are laspj_nif.hip's run().
 
 #include "laspj_nif_internal.h"
@@ -7,9 +7,14 @@
 namespace laspj {
 namespace {
 
-// lasp_orset:update/3 / lasp_gset:update/3 (lasp_orset.erl:99-117, 222-259;
-// lasp_gset.erl:84-88) of one call on a resident variable's cells: the ops in order, all or
-// nothing.  A REMOVE whose element is absent — not in the cells and not added earlier in the
+// lasp_core:update/4 (lasp_core.erl:283-312) of one call on a resident variable's cells:
+// Type:update/3 (lasp_orset.erl:99-117, 222-259; lasp_gset.erl:84-88) — the ops in order, all
+// or nothing — then bind/3 of its Value, which writes merge(Value0, Value).  lasp_orset:merge
+// ORs the flags of a token both hold (lasp_orset.erl:128-136), so per token bit the call gives
+// p' = p0 | pV, r' = r0 | rV: an ADD by a token Value0 holds removed leaves it removed (update/3
+// alone stores `false`, the bind's merge makes it `true` again), and an ADD after a REMOVE of
+// its element in the same call takes the bit back to r0, not to the 1 the REMOVE put there.
+// A REMOVE whose element is absent — not in the cells and not added earlier in the
 // call — fails the call ({error, {precondition, {not_present, E}}}, remove_elems / apply_ops
 // stop there and the state is kept); element 0xFFFFFFFF is an element the dictionary has
 // never held.  Few ops travel as kernel arguments (no upload on the update path); one lane
@@ -45,6 +50,17 @@ __global__ void __launch_bounds__(64) k_var_update(uint64_t* __restrict__ cells,
             if (!present) bad = k;
         }
     }
+    // a call with a REMOVE (status is its answer array): every ADD's removed bit as Value0
+    // has it, read before the first op lands and parked in the op's status word
+    const bool keep_r0 = kind == LASPJ_KIND_ORSET && status && bad == nops;
+    if (keep_r0)
+        for (uint32_t k = 0; k < nops; ++k) {
+            const laspj_op o = op(k);
+            if (o.kind != LASPJ_OP_ADD) continue;
+            const uint32_t t = op_slot(o);
+            status[k] = (int32_t)(cells[2ull * ((uint64_t)o.element * tw + (t >> 6)) + 1] >>
+                                  (t & 63u) & 1u);
+        }
     for (uint32_t k = 0; k < nops; ++k) {
         if (bad < nops) {
             if (status) status[k] = k == bad ? LASPJ_OPST_NOT_PRESENT : LASPJ_OPST_ROLLED_BACK;
@@ -54,10 +70,15 @@ __global__ void __launch_bounds__(64) k_var_update(uint64_t* __restrict__ cells,
         if (kind == LASPJ_KIND_ORSET) {
             uint64_t* c = cells + 2ull * (uint64_t)o.element * tw;
             if (o.kind == LASPJ_OP_ADD) {
-                // orddict:store(Token, false, Tokens): present, flag false
+                // orddict:store(Token, false, Tokens) merged with Value0: present, the flag
+                // Value0's (without a REMOVE in the call the word still holds it)
                 const uint32_t t = op_slot(o);
-                c[2 * (t >> 6)] |= 1ull << (t & 63u);
-                c[2 * (t >> 6) + 1] &= ~(1ull << (t & 63u));
+                const uint64_t bit = 1ull << (t & 63u);
+                c[2 * (t >> 6)] |= bit;
+                if (keep_r0) {
+                    uint64_t& r = c[2 * (t >> 6) + 1];
+                    r = status[k] ? r | bit : r & ~bit;
+                }
             } else {
                 for (uint32_t j = 0; j < tw; ++j)
                     c[2 * j + 1] = c[2 * j];           // every token of Elem := true
@@ -69,7 +90,8 @@ __global__ void __launch_bounds__(64) k_var_update(uint64_t* __restrict__ cells,
     }
 }
 
-// the same for a call of ADDs only (add_all over many elements): commutative, one op per lane
+// the same for a call of ADDs only (add_all over many elements): commutative, one op per
+// lane; with no REMOVE in the call every removed bit stays Value0's
 __global__ void __launch_bounds__(256) k_var_adds(uint64_t* __restrict__ cells, int32_t kind,
                                                   uint32_t tw, const laspj_op* __restrict__ ops,
                                                   uint32_t nops) {
@@ -81,7 +103,6 @@ __global__ void __launch_bounds__(256) k_var_adds(uint64_t* __restrict__ cells, 
         unsigned long long* c = reinterpret_cast<unsigned long long*>(
             cells + 2ull * ((uint64_t)o.element * tw + (t >> 6)));
         atomicOr(c, 1ull << (t & 63u));
-        atomicAnd(c + 1, ~(1ull << (t & 63u)));
     } else {
         atomicOr(reinterpret_cast<unsigned long long*>(cells + (o.element >> 6)),
                  1ull << (o.element & 63u));

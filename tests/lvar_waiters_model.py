@@ -10,8 +10,8 @@ ReplyModel over tests/lvars_model.threshold.
 """
 
 import lvars_model as lm
+import update4_model as um
 import waiters_model as wm
-from oracle import orset as oorset
 from oracle.terms import Atom
 
 A = Atom
@@ -190,7 +190,7 @@ class ListScenario(wm.Scenario):
         else:
             e = rng.choice(self.ELEMS)
             op = (A("add_by_token"), self.tok_for(e, 0.8), e)
-        want = oorset.update(op, A("a"), cur)
+        want = um.update4("orset", op, cur, [])
         if self.devs is not None:
             var = self.devs.l if left else self.devs.r
             verd, res, _err, _minted = var.update(tb(op))

@@ -9,9 +9,8 @@ import random
 import pytest
 
 import filters_model as fm
+import update4_model as um
 from oracle import etf as oetf
-from oracle import gset as ogset
-from oracle import orset as oorset
 from oracle.terms import Atom, exact_eq
 
 OK, FALLBACK = 0, 1
@@ -35,13 +34,11 @@ def _status(exc) -> int:
 
 
 def upd(var, cur, op, type_="lasp_orset"):
-    """update/4 on the device variable and, with the tokens it minted, on the oracle."""
+    """update/4 on the device variable and, with the tokens it minted, on the model
+    (tests/update4_model.py: update/3, then the bind's merge with cur)."""
     verd, res, _err, minted = var.update(tb(op))
     assert verd == OK, op
-    if type_ == "lasp_gset":
-        return ogset.update(op, A("a"), cur)[1]
-    it = iter(minted)
-    want = oorset.update(op, A("a"), cur, tokens=lambda _actor: next(it))
+    want = um.update4(type_, op, cur, minted)
     assert (res == 0) == (want[0] == "ok"), op
     return want[1] if want[0] == "ok" else cur
 
@@ -486,5 +483,33 @@ def test_filter_create_errors():
             assert _status(ex) == want
         ctx.filter(o, o.replica()).close()
         ctx.filter(g, g).close()
+    finally:
+        ctx.close()
+
+
+def test_readd_by_a_removed_token_is_no_new_input():
+    """update/4 is update/3 then the bind's merge (lasp_core.erl:283-312): an add_by_token by
+    a token in holds removed, and a remove then an add_by_token of an element's only token
+    in one call, leave in as it was — the re-run answers what the model answers, a no-op,
+    and out reads as before."""
+    ctx = _ctx()
+    try:
+        inv = ctx.var("orset")
+        tok = lambda k: bytes([k]) * 20                  # noqa: E731
+        value = []
+        for e in range(7):
+            value = upd(inv, value, (A("add_by_token"), tok(e), e))
+        value = upd(inv, value, (A("remove"), 3))
+        p = Proc(ctx, "lasp_orset", inv, inv.replica(), lambda e: e % 3 == 0)
+        assert p.step(value) == WRITTEN
+        before = p.out_var.read()
+        assert before == (OK, tb([(0, [(tok(0), False)]), (3, [(tok(3), True)]),
+                                  (6, [(tok(6), False)])]))
+        for op in ((A("add_by_token"), tok(3), 3),
+                   (A("update"), [(A("remove"), 6), (A("add_by_token"), tok(6), 6)])):
+            assert upd(inv, value, op) == value
+            assert inv.read() == (OK, tb(value)), op
+            assert p.run(value, op) == (NOOP, 0)
+            assert p.out_var.read() == before, op
     finally:
         ctx.close()

@@ -11,6 +11,7 @@ import pytest
 
 import lvar_waiters_model as lwm
 import lvars_model as lm
+import update4_model as um
 from oracle.terms import Atom
 
 OK, FALLBACK = 0, 1
@@ -277,7 +278,7 @@ def test_fused_rerun_equals_the_two_calls():
             nonlocal lval, rval
             add(d.l if left else d.r, e, t)
             cur = lval if left else rval
-            new = lwm.oorset.update((A("add_by_token"), t, e), A("a"), cur)[1]
+            new = um.update4("orset", (A("add_by_token"), t, e), cur, [])[1]
             if left:
                 lval = new
             else:
@@ -319,7 +320,7 @@ def test_fused_rerun_equals_the_two_calls():
         for k in range(4):
             e = 6 + k % 3
             wait(lm.bind(m.value, lm.acc_value(
-                lwm.oorset.update((A("add_by_token"), tok(40 + k), e), A("a"), lval)[1],
+                um.update4("orset", (A("add_by_token"), tok(40 + k), e), lval, [])[1],
                 rval))[1], k % 2 == 0)
             wait([(e, [(tok(40 + k), False)])], False)
             upd(True, e, tok(40 + k))

@@ -10,6 +10,7 @@ import random
 import pytest
 
 import lvars_model as lm
+import update4_model as um
 from oracle import etf as oetf
 from oracle import orset as oorset
 from oracle.terms import Atom
@@ -32,11 +33,11 @@ def _ctx():
 
 
 def upd(var, cur, op):
-    """update/4 on the device variable and, with the tokens it minted, on the oracle."""
+    """update/4 on the device variable and, with the tokens it minted, on the model
+    (tests/update4_model.py: update/3, then the bind's merge with cur)."""
     verd, res, _err, minted = var.update(tb(op))
     assert verd == OK, op
-    it = iter(minted)
-    want = oorset.update(op, A("a"), cur, tokens=lambda _actor: next(it))
+    want = um.update4("orset", op, cur, minted)
     assert (res == 0) == (want[0] == "ok"), op
     return want[1] if want[0] == "ok" else cur
 
@@ -455,5 +456,35 @@ def test_every_fallback_cause_leaves_out_unchanged():
         # until the next write
         assert out.write(tb(cur)) == OK and out.resident
         assert rerun(out, l, r, lval, rval, cur)[0] == NOOP
+    finally:
+        ctx.close()
+
+
+def test_readd_by_a_removed_token_is_no_new_input():
+    """update/4 is update/3 then the bind's merge (lasp_core.erl:283-312): an add_by_token by
+    a token in holds removed, and a remove then an add_by_token of an element's only token
+    in one call, leave l as it was — the re-run answers what the model answers, a no-op,
+    and out reads as before."""
+    ctx = _ctx()
+    try:
+        l = ctx.var("orset")
+        r = l.replica()
+        out = ctx.list_var(l)
+        lval, rval = [], []
+        for e in range(6):
+            lval = upd(l, lval, (A("add_by_token"), tok(e), e))
+        for e in range(2, 8):
+            rval = upd(r, rval, (A("add_by_token"), tok(100 + e), e))
+        lval = upd(l, lval, (A("remove"), 3))
+        st, cur = rerun(out, l, r, lval, rval, [])
+        assert st == WRITTEN and [k for k, _t in cur] == [2, 3, 4, 5]
+        before = out.read()
+        for op in ((A("add_by_token"), tok(3), 3),
+                   (A("update"), [(A("remove"), 4), (A("add_by_token"), tok(4), 4)])):
+            assert upd(l, lval, op) == lval
+            assert l.read() == (OK, tb(lval)), op
+            assert rerun(out, l, r, lval, rval, cur, op) == (NOOP, cur)
+            check(out, cur, op)
+            assert out.read() == before, op
     finally:
         ctx.close()

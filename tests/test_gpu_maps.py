@@ -11,8 +11,8 @@ import pytest
 
 import lvars_model as lm
 import maps_model as mm
+import update4_model as um
 from oracle import etf as oetf
-from oracle import orset as oorset
 from oracle.terms import Atom
 
 OK, FALLBACK = 0, 1
@@ -37,11 +37,11 @@ def tok(k: int) -> bytes:
 
 
 def upd(var, cur, op):
-    """update/4 on the device variable and, with the tokens it minted, on the oracle."""
+    """update/4 on the device variable and, with the tokens it minted, on the model
+    (tests/update4_model.py: update/3, then the bind's merge with cur)."""
     verd, res, _err, minted = var.update(tb(op))
     assert verd == OK, op
-    it = iter(minted)
-    want = oorset.update(op, A("a"), cur, tokens=lambda _actor: next(it))
+    want = um.update4("orset", op, cur, minted)
     assert (res == 0) == (want[0] == "ok"), op
     return want[1] if want[0] == "ok" else cur
 
@@ -537,3 +537,30 @@ def test_lifecycle():
     with pytest.raises(LaspjError):
         c.run()
     c.close()
+
+
+def test_readd_by_a_removed_token_is_no_new_input():
+    """update/4 is update/3 then the bind's merge (lasp_core.erl:283-312): an add_by_token by
+    a token in holds removed, and a remove then an add_by_token of an element's only token
+    in one call, leave in as it was — the re-run answers what the model answers, a no-op,
+    and out reads as before."""
+    ctx = _ctx()
+    try:
+        inv = ctx.var("orset")
+        value = []
+        for e in range(6):
+            value = upd(inv, value, (A("add_by_token"), tok(e), e))
+        value = upd(inv, value, (A("remove"), 3))
+        p = Proc(ctx, inv, lambda x: x + 100)
+        assert p.step(value) == WRITTEN
+        before = p.lv.read()
+        for op in ((A("add_by_token"), tok(3), 3),
+                   (A("update"), [(A("remove"), 2), (A("add_by_token"), tok(2), 2)])):
+            assert upd(inv, value, op) == value
+            assert inv.read() == (OK, tb(value)), op
+            assert p.run(value, op) == (NOOP, 0)
+            p.check_out(op)
+            assert p.lv.read() == before, op
+        p.close()
+    finally:
+        ctx.close()

@@ -20,6 +20,7 @@ import random
 
 import pytest
 
+import update4_model as um
 from oracle import etf as oetf
 from oracle import gset as ogset
 from oracle import lattice as olat
@@ -45,11 +46,9 @@ def _ctx():
 
 
 def _oracle_update(mod, op, state, minted):
-    """Type:update/3 on the oracle with the tokens the device minted, in op order."""
-    it = iter(minted)
-    if mod is ogset:
-        return ogset.update(op, A("a"), state)
-    return oorset.update(op, A("a"), state, tokens=lambda _actor: next(it))
+    """update/4 on the model (tests/update4_model.py) with the tokens the device minted, in
+    op order: Type:update/3, then the bind's merge with the value held."""
+    return um.update4("gset" if mod is ogset else "orset", op, state, minted)
 
 
 def _elements(rng):
@@ -76,8 +75,9 @@ def _rand_op(rng, elems, toks, depth=0):
 def test_var_update_random_ops_match_oracle():
     """300 random update/4 calls on a resident OR-Set variable (every op form, nested
     {update, Ops}, removes of absent elements, re-adds by a known token): the result, the
-    failing element and the value read back agree with lasp_orset:update/3 replayed on the
-    oracle with the minted tokens; value/1 and threshold_met agree along the way."""
+    failing element and the value read back agree with update/4 (lasp_orset:update/3, then
+    the bind's merge) replayed on the oracle with the minted tokens; value/1 and
+    threshold_met agree along the way."""
     ctx = _ctx()
     try:
         rng = random.Random(61)
@@ -141,9 +141,12 @@ def test_var_update_preconditions_void_the_call():
         assert (verd, res) == (OK, UPD_OK)
         want = oorset.merge(before, [(5, [(t2, True)])])
         assert var.read() == (OK, _tb(want))
-        # a re-add by a known token clears its removed flag (orddict:store(Token, false, ..))
+        # a re-add by a known removed token leaves it removed: update/3 stores it `false`
+        # and the bind's merge with the value held ORs the flags (lasp_core.erl:283-312,
+        # lasp_orset.erl:128-136)
         assert var.update(_tb((A("add_by_token"), t2, 5)))[:2] == (OK, UPD_OK)
-        assert var.read() == (OK, _tb(oorset.merge(before, [(5, [(t2, False)])])))
+        assert var.read() == (OK, _tb(want))
+        assert var.value() == (OK, _tb([1]))
     finally:
         ctx.close()
 
@@ -167,10 +170,10 @@ def test_var_update_gset_and_fallbacks():
                 op = (A("add"), rng.choice([rng.randrange(300), A(f"g{k % 5}"), (k % 4, b"x")]))
             verd, res, err, minted = g.update(_tb(op))
             assert (verd, res, minted) == (OK, UPD_OK, []), op
-            cur = ogset.update(op, A("a"), cur)[1]
+            cur = _oracle_update(ogset, op, cur, minted)[1]
             assert g.read() == (OK, _tb(cur)), (k, op)
         assert g.update(_tb((A("add"), 1)))[:2] == (OK, UPD_OK)
-        cur = ogset.update((A("add"), 1), A("a"), cur)[1]
+        cur = _oracle_update(ogset, (A("add"), 1), cur, [])[1]
         for op in ((A("remove"), 1), (A("add_all"), A("x")), (A("nope"), 1), (A("add"), 1.0)):
             assert g.update(_tb(op))[0] == FALLBACK, op
             assert g.read() == (OK, _tb(cur))

@@ -10,6 +10,7 @@ to, in list order, and the rest stay in order.  ReplyModel is that, over oracle.
 
 import random
 
+import update4_model as um
 from oracle import etf as oetf
 from oracle import gset as ogset
 from oracle import lattice as olat
@@ -62,10 +63,8 @@ class ReplyModel:
 
 
 def oracle_update(kind, op, state, minted):
-    it = iter(minted)
-    if kind == "gset":
-        return ogset.update(op, A("a"), state)
-    return oorset.update(op, A("a"), state, tokens=lambda _actor: next(it))
+    """update/4 (tests/update4_model.py): Type:update/3, then the bind's merge with `state`."""
+    return um.update4(kind, op, state, minted)
 
 
 def merge(kind, a, b):
