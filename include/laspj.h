@@ -1262,8 +1262,14 @@ int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found);
  * image, the other calls FALLBACK).  Its `#dv.waiting_threads` are kept beside it
  * (laspj_lvar_wait and the calls after it): a waiter's threshold is walked once into a device
  * list of its own and all of a variable's waiters are re-checked in one device pass, which
- * the intersection's re-run can carry inside its own synchronisation.  Lazy threads are not
- * kept for it.  Every call takes the context's call lock, never the group-commit queue.
+ * the intersection's re-run can carry inside its own synchronisation.  Its `#dv.lazy_threads`
+ * are kept the same way (laspj_lvar_wait_needed and the calls after it): a lazy threshold is a
+ * device list of its own too, and a read checks the value and every lazy threshold against
+ * its own threshold in one device pass.  Every call that answers LASPJ_BIND_WRITTEN on a list
+ * variable (laspj_lvar_intersection, laspj_lvar_intersection_recheck, laspj_lvar_etf_bind,
+ * laspj_map_run, laspj_fold_run) and laspj_lvar_etf_write empty its lazy list (write/4 builds
+ * a fresh #dv, lasp_core.erl:842-843); LASPJ_BIND_NOOP and LASPJ_BIND_REFUSED leave it alone.
+ * Every call takes the context's call lock, never the group-commit queue.
  * After the context is gone every call answers LASPJ_E_INVAL and destroy still frees. */
 typedef struct laspj_lvar laspj_lvar;
 /* bind/3's third outcome (lasp_core.erl:301-307): merge(Value0, Value) is not an inflation
@@ -1361,6 +1367,60 @@ int laspj_lvar_waiter_count(const laspj_lvar* lv, uint32_t* n);
  * call); LASPJ_E_RANGE past the last.  The NIF's walk behind a FALLBACK verdict. */
 int laspj_lvar_waiter_at(laspj_lvar* lv, uint32_t k, uint64_t* id, int32_t* strict,
                          const uint8_t** threshold, uint64_t* n);
+/* wait_needed/6 (lasp_core.erl:730-758) on a list variable: the threshold is walked into a
+ * list over the namespace and threshold_met(lasp_orset, #dv.value, Threshold)
+ * (lasp_lattice.erl:62-75) is answered as laspj_lvar_wait answers it.  Met -> *needed = 1,
+ * nothing kept; unmet with a non-empty waiting_threads (:739-741) -> *needed = 1, nothing
+ * kept; unmet otherwise -> the walked list becomes the device list of the lazy entry {id,
+ * Threshold}, appended to `#dv.lazy_threads`, and *needed = 0.  strict = 1 that would
+ * register: the stored {strict, T} is later handed to the list clauses as a value (:798) and
+ * crashes in lists:keyfind — verdict FALLBACK, nothing kept.  FALLBACK also where
+ * laspj_lvar_etf_threshold answers it: an image the walk refuses, a wide namespace, a
+ * host-held value. */
+int laspj_lvar_wait_needed(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict,
+                           uint64_t id, int32_t* needed, int32_t* verdict);
+/* read/6 (lasp_core.erl:331-364) on a list variable, lazy threads included, with
+ * laspj_var_read's contract (the caller has replaced `undefined` by []).  One device pass
+ * answers threshold_met(Value, Threshold) (:352) and, for every lazy entry j,
+ * threshold_met(LazyThreshold_j, Threshold) (:348-349, 795-813; lasp_lattice.erl:72-75,
+ * 153-161, 235-253) — is_inflation, or is_strict_inflation for a strict read, from the read's
+ * threshold to the lazy one: a first-match table per list, one check launch over every
+ * pair, one finish launch, one synchronisation.  The fired ids go to lazy_ids[0 .. *nlazy) in
+ * list order.  More fired than cap: no waiter or lazy entry is added or removed, *nlazy > cap
+ * says how much room to come back with.  Met -> *met = 1 and the lazy list is exactly as it
+ * was (:353-354: the fired entries stay and fire again on the next read); unmet -> *met = 0,
+ * the waiter {id, strict, Threshold} is appended (the waiter laspj_lvar_wait makes:
+ * laspj_lvar_recheck serves it) and the fired entries leave (:362).  *nstill_lazy: the lazy
+ * list's length after the call.  With an empty lazy list the answers and the kept waiter are
+ * laspj_lvar_wait's.  verdict FALLBACK, nothing changed: laspj_lvar_wait's cases, and a lazy
+ * entry that went stale at a dictionary reset and whose image the walk now refuses. */
+int laspj_lvar_read(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                    int32_t* met, uint64_t* lazy_ids, uint32_t cap, uint32_t* nlazy,
+                    uint32_t* nstill_lazy, int32_t* verdict);
+/* read_any/3 (lasp_core.erl:371-420) over n {list variable, threshold} pairs of one context:
+ * the fold of :372-414, with laspj_var_read_any's *found, nlazy[i], grouping of lazy_ids and
+ * cap rule.  All n thresholds are walked first, each into a list of its own; then one device
+ * pass (one per namespace named) checks every (read, value) and (read, lazy threshold) pair,
+ * and the fold runs on the host over the met bytes — the pass may test pairs the fold then
+ * ignores.  A variable may be named again: a later read of it sees the earlier read's waiter
+ * and removals.  One verdict for the call: FALLBACK, nothing changed, where laspj_lvar_read
+ * answers it for any read.  A variable of another context: LASPJ_E_INVAL.  Canonical and list
+ * variables are not mixed in one call: the NIF serves such a read_any as the fold itself,
+ * laspj_var_read / laspj_lvar_read in order with one id until one is met. */
+int laspj_lvar_read_any(laspj_ctx* ctx, uint32_t n, laspj_lvar* const* lvs,
+                        const uint8_t* const* thresholds, const uint64_t* lens,
+                        const int32_t* strict, uint64_t id, int32_t* found, uint64_t* lazy_ids,
+                        uint32_t cap, uint32_t* nlazy, int32_t* verdict);
+/* length(`#dv.lazy_threads`) (include/lasp.hrl:60-63) of a list variable */
+int laspj_lvar_lazy_count(const laspj_lvar* lv, uint32_t* n);
+/* the k-th lazy entry of a list variable in list order (lasp_core.erl:795-813 walks them so):
+ * its id and its threshold image as registered (valid until the variable's next waiter or
+ * lazy call); LASPJ_E_RANGE past the last.  The NIF's walk behind a FALLBACK verdict. */
+int laspj_lvar_lazy_at(laspj_lvar* lv, uint32_t k, uint64_t* id, const uint8_t** threshold,
+                       uint64_t* n);
+/* a lazy entry leaves (its process died, or the NIF's own walk replied to it): the first with
+ * that id of `#dv.lazy_threads` (include/lasp.hrl:60-63); *found 0 when there is none */
+int laspj_lvar_lazy_cancel(laspj_lvar* lv, uint64_t id, int32_t* found);
 /* length(#dv.value) and its tokens over all entries (include/lasp.hrl:60-63); a host-held
  * value: LASPJ_E_UNSUPPORTED */
 int laspj_lvar_counts(laspj_lvar* lv, uint32_t* entries, uint32_t* tokens);

@@ -275,6 +275,15 @@ SIGNATURES = {
     "laspj_lvar_waiter_count": (i, [vp, C.POINTER(u32)]),
     "laspj_lvar_waiter_at": (i, [vp, u32, C.POINTER(u64), C.POINTER(C.c_int32), vpp,
                                  C.POINTER(u64)]),
+    "laspj_lvar_wait_needed": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32)]),
+    "laspj_lvar_read": (i, [vp, vp, u64, i, u64, C.POINTER(C.c_int32), vp, u32, C.POINTER(u32),
+                            C.POINTER(u32), C.POINTER(C.c_int32)]),
+    "laspj_lvar_read_any": (i, [vp, u32, vp, vp, vp, vp, u64, C.POINTER(C.c_int32), vp, u32, vp,
+                                C.POINTER(C.c_int32)]),
+    "laspj_lvar_lazy_count": (i, [vp, C.POINTER(u32)]),
+    "laspj_lvar_lazy_at": (i, [vp, u32, C.POINTER(u64), vpp, C.POINTER(u64)]),
+    "laspj_lvar_lazy_cancel": (i, [vp, u64, C.POINTER(C.c_int32)]),
     "laspj_lvar_counts": (i, [vp, C.POINTER(u32), C.POINTER(u32)]),
     "laspj_lvar_resident": (i, [vp, C.POINTER(C.c_int32)]),
     "laspj_map_create": (i, [vp, vp, vpp]),

@@ -720,6 +720,25 @@ struct ListWaiter {
 };
 int list_waiters_check(laspj_ctx* ctx, const laspj_batch* value, const laspj_list_order* ord,
                        const ListWaiter* ws, uint32_t W, uint8_t* met);
+// read/6's and read_any/3's tests (lasp_core.erl:331-364, 371-420) on list variables, the
+// transpose of the waiter check: pair k asks whether current pairs[k].cur — a variable's
+// value, or one of its lazy thresholds (reply_to_all's wait clause, :795-813) — inflates
+// read pairs[k].read's threshold (strict: strictly), met[k] the answer.  reads: R thresholds
+// (ListWaiter: list, entries, strict); curs: C one-replica OR-Set LIST batches, n the host's
+// count of each one's entries.  One pass: a memset, a first-match table per current built by
+// one insert launch, one check launch over tiles of kLwTile threshold entries of all pairs,
+// a one-block finish launch that writes the met bytes into pinned memory, one
+// synchronisation.  R, C, P >= 1.
+struct ListReadCur {
+    const laspj_batch* list;
+    uint32_t n;
+};
+struct ListReadPair {
+    uint32_t read, cur;
+};
+int list_reads_check(laspj_ctx* ctx, const laspj_list_order* ord, const ListWaiter* reads,
+                     uint32_t R, const ListReadCur* curs, uint32_t C, const ListReadPair* pairs,
+                     uint32_t P, uint8_t* met);
 // laspj_list_bind of one-replica lists with a tail: the check pass of ws against dst (the
 // merge) enqueued behind the bind's last kernel and ahead of its one synchronisation (again
 // behind the merge path when the rank-indexed bind answers retry); met is written only when

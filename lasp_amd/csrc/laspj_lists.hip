@@ -1846,6 +1846,133 @@ __global__ __launch_bounds__(256) void k_lw_finish(LV val, RK rk, LwPass p) {
     if (threadIdx.x == 0) *p.err_out = *rk.flag;
 }
 
+// ---------------------------------------------------------------- a list variable's reads
+// read/6 and read_any/3 (lasp_core.erl:331-364, 371-420) on list-valued variables: the
+// transpose of the waiter pass.  P pairs (read i, current c) are answered at once, where the
+// read's threshold T_i is the previous state and the current is a variable's value
+// (threshold_met(Value, T), :352) or one of its lazy thresholds (reply_to_all's wait clause,
+// :795-813: threshold_met(Lazy_j, T)).  Every current gets a first-match table of its own in
+// one zeroed block (k_lr_insert: a work item is one tile of 256 entries of one current, found
+// by binary search over its item0), k_lr_check runs k_lw_check's per-entry body for one tile
+// of kLwTile entries of T_i of one pair against that pair's table, and the one-block
+// k_lr_finish applies k_lw_finish's rule per pair with np = T_i's entries and nc = the
+// current's — a T_i with no entries has no item and is answered there — and writes the P met
+// bytes and the error word into pinned memory.  No wave waits for another.  Every count and
+// token offset read from a current is clamped to the host's count and the list's capacity.
+struct LrCur {
+    const u64* key;
+    const u64* tok;
+    const uint32_t* toff;
+    const uint32_t* hdr;
+    uint32_t n;                 // the host's count of its entries (<= its capacity)
+    uint32_t ct;                // its token capacity
+    uint32_t hoff, hsize;       // its table: hsize slots from slot hoff of the pass's tables
+};
+static_assert(sizeof(LrCur) == 48, "descriptor layout");
+
+struct LrPair {
+    uint32_t read, cur;
+};
+
+struct LrPass {
+    const LwDesc* rd;           // R reads' thresholds
+    const LrCur* cur;           // C currents
+    const LrPair* pair;         // P pairs
+    const uint32_t* citem0;     // C + 1: current c's first insert item
+    const uint32_t* pitem0;     // P + 1: pair k's first check item
+    uint32_t C, P;
+    u64* hk;                    // all tables, zero on entry
+    uint32_t* hi;
+    uint32_t* flags;            // P words, zero on entry
+    uint8_t* met;               // P bytes (pinned)
+    uint32_t* err_out;          // rk.flag's word copied beside them
+};
+
+// the owner of work item `item`: the last k < n whose first item is not past it
+__device__ __forceinline__ uint32_t lr_owner(const uint32_t* item0, uint32_t n, uint32_t item) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (item0[mid] <= item) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint32_t lr_count(const LrCur& c) {
+    const uint32_t n = c.hdr[0];
+    return n < c.n ? n : c.n;
+}
+
+__global__ __launch_bounds__(256) void k_lr_insert(RK rk, LrPass p) {
+    const uint32_t item = blockIdx.x, ci = lr_owner(p.citem0, p.C, item);
+    const LrCur c = p.cur[ci];
+    const uint32_t i = (item - p.citem0[ci]) * 256 + threadIdx.x;
+    if (i < lr_count(c))
+        h_insert(p.hk + c.hoff, p.hi + c.hoff, c.hsize - 1, key_ord(c.key[i], rk), i);
+}
+
+__global__ __launch_bounds__(kLwTile) void k_lr_check(RK rk, LrPass p) {
+    const uint32_t item = blockIdx.x, k = lr_owner(p.pitem0, p.P, item);
+    const LrPair pr = p.pair[k];
+    const LwDesc d = p.rd[pr.read];
+    const LrCur c = p.cur[pr.cur];
+    const uint32_t i = (item - p.pitem0[k]) * kLwTile + threadIdx.x;
+    const uint32_t nc = lr_count(c);
+    bool viol = false, changed = false;
+    if (i < d.n) {
+        // lists:keyfind(Element, 1, Current): the first entry with an equal key
+        const uint32_t j = h_find(p.hk + c.hoff, p.hi + c.hoff, c.hsize - 1, key_ord(d.key[i], rk));
+        if (j == kNone || j >= nc) {
+            viol = true;
+        } else {
+            const u64* tp = d.tok + d.toff[i];
+            const uint32_t lp = d.toff[i + 1] - d.toff[i];
+            uint32_t c1 = c.toff[j + 1], c0 = c.toff[j];
+            c1 = c1 < c.ct ? c1 : c.ct;
+            c0 = c0 < c1 ? c0 : c1;
+            const u64* tc = c.tok + c0;
+            const uint32_t lc = c1 - c0;
+            // ids_inflated: every threshold token keyfind-s among the current's (flags ignored)
+            for (uint32_t x = 0; x < lp && !viol; ++x) {
+                const u64 ox = tok_ord(tp[x], rk);
+                bool found = false;
+                for (uint32_t y = 0; y < lc && !found; ++y) found = tok_ord(tc[y], rk) == ox;
+                viol = !found;
+            }
+            // DeletedElements: Ids =/= Ids1 (order- and flag-sensitive)
+            if (d.strict) {
+                if (lp != lc) {
+                    changed = true;
+                } else {
+                    for (uint32_t x = 0; x < lp && !changed; ++x)
+                        changed = tok_ord(tp[x], rk) != tok_ord(tc[x], rk) ||
+                                  ((tp[x] ^ tc[x]) & kRemoved) != 0;
+                }
+            }
+        }
+    }
+    const uint32_t f = (viol ? kViolBit : 0u) | (changed ? kChangedBit : 0u);
+    const u64 any = __ballot(f != 0);
+    uint32_t wf = f;
+    for (int off = 32; off > 0; off >>= 1) wf |= __shfl_xor(wf, off, 64);
+    if (any && lane_id() == 0) atomicOr(p.flags + k, wf);
+}
+
+__global__ __launch_bounds__(256) void k_lr_finish(RK rk, LrPass p) {
+    for (uint32_t k = threadIdx.x; k < p.P; k += 256) {
+        const LrPair pr = p.pair[k];
+        const uint32_t np = p.rd[pr.read].n, nc = lr_count(p.cur[pr.cur]), f = p.flags[k];
+        bool res = !(f & kViolBit);
+        if (p.rd[pr.read].strict) {
+            if (np == 0 && nc != 0) res = true;            // ([], Current) when Current =/= []
+            else res = res && ((f & kChangedBit) != 0 || np < nc);   // NewElements: length/1
+        }
+        p.met[k] = res ? 1 : 0;
+    }
+    if (threadIdx.x == 0) *p.err_out = *rk.flag;
+}
+
 // ---------------------------------------------------------------- tiled producers
 // Every producer below emits, per replica, a compaction of one input sequence in order:
 // item i of replica r emits ne_i entries and nt_i tokens at the exclusive prefix sums of
@@ -3173,6 +3300,26 @@ static int grow_block(laspj_ctx* ctx, void** p, uint64_t* have, uint64_t bytes, 
 // the met bytes and the error word of W waiters in the pass's pinned block
 static uint64_t lw_err_at(uint32_t W) { return ((uint64_t)W + 3) & ~3ull; }
 
+// the pass's pinned block (ctx->lw_h, coherent) holds at least hbytes
+static int lw_answers(laspj_ctx* ctx, uint64_t hbytes, const char* what) {
+    if (ctx->lw_h_bytes >= hbytes) return LASPJ_OK;
+    if (ctx->lw_h) {
+        hipStreamSynchronize(ctx->stream);
+        hipHostFree(ctx->lw_h);
+        ctx->lw_h = nullptr;
+        ctx->lw_h_bytes = 0;
+    }
+    const uint64_t want = std::max<uint64_t>(hbytes, 4096);
+    if (hipHostMalloc(&ctx->lw_h, want, hipHostMallocCoherent) != hipSuccess) {
+        hipGetLastError();
+        ctx->lw_h = nullptr;
+        return fail(ctx, LASPJ_E_NOMEM, "%s: pinned answers", what);
+    }
+    ctx->lw_h_bytes = want;
+    LJ_HIP(ctx, hipHostGetDevicePointer(&ctx->lw_hd, ctx->lw_h, 0));
+    return LASPJ_OK;
+}
+
 // The waiter check of ws against `value` enqueued on the context's stream (ctx->mu held): a
 // memset of the pass's own zeroed block, k_lw_insert, k_lw_check, k_lw_finish.  ub_e: the
 // value holds at most that many entries (its table is sized from it).  The descriptors go
@@ -3209,23 +3356,7 @@ static int list_waiters_enqueue(laspj_ctx* ctx, const laspj_batch* value, uint64
     if (int s = grow_block(ctx, &ctx->lw_dev, &ctx->lw_dev_bytes, zbytes + ((dbytes + 255) & ~255ull),
                            false, what))
         return s;
-    const uint64_t hbytes = lw_err_at(W) + 4;
-    if (ctx->lw_h_bytes < hbytes) {
-        if (ctx->lw_h) {
-            hipStreamSynchronize(ctx->stream);
-            hipHostFree(ctx->lw_h);
-            ctx->lw_h = nullptr;
-            ctx->lw_h_bytes = 0;
-        }
-        const uint64_t want = std::max<uint64_t>(hbytes, 4096);
-        if (hipHostMalloc(&ctx->lw_h, want, hipHostMallocCoherent) != hipSuccess) {
-            hipGetLastError();
-            ctx->lw_h = nullptr;
-            return fail(ctx, LASPJ_E_NOMEM, "%s: pinned answers", what);
-        }
-        ctx->lw_h_bytes = want;
-        LJ_HIP(ctx, hipHostGetDevicePointer(&ctx->lw_hd, ctx->lw_h, 0));
-    }
+    if (int s = lw_answers(ctx, lw_err_at(W) + 4, what)) return s;
     char* base = static_cast<char*>(ctx->lw_dev);
     const char* ddev = nullptr;
     if (const void* slot = laspj::stage_small(ctx, blob.data(), dbytes))
@@ -3288,6 +3419,102 @@ int list_waiters_check(laspj_ctx* ctx, const laspj_batch* value, const laspj_lis
         return s;
     LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return list_waiters_answer(ctx, W, met, "list_waiters");
+}
+
+int list_reads_check(laspj_ctx* ctx, const laspj_list_order* ord, const ListWaiter* reads,
+                     uint32_t R, const ListReadCur* curs, uint32_t C, const ListReadPair* pairs,
+                     uint32_t P, uint8_t* met) {
+    const char* what = "list_reads";
+    if (!ctx || !reads || !curs || !pairs || !met || !R || !C || !P)
+        return fail(ctx, LASPJ_E_INVAL, "list_reads: null argument");
+    RK rk;
+    if (int s = ranks(ctx, ord, true, &rk, what)) return s;
+    auto one_list = [&](const laspj_batch* b, uint32_t n) {
+        return b && b->ctx == ctx && b->kind == LASPJ_KIND_ORSET_LIST && b->replicas == 1 &&
+               n <= b->cap_e;
+    };
+    // descriptors: [LwDesc x R | LrCur x C | LrPair x P | citem0 x (C + 1) | pitem0 x (P + 1)]
+    const uint64_t o_cur = 32ull * R, o_pair = o_cur + 48ull * C, o_ci = o_pair + 8ull * P,
+                   o_pi = o_ci + 4ull * (C + 1ull), dbytes = o_pi + 4ull * (P + 1ull);
+    std::vector<uint8_t> blob(dbytes);
+    auto* hr = reinterpret_cast<LwDesc*>(blob.data());
+    auto* hc = reinterpret_cast<LrCur*>(blob.data() + o_cur);
+    auto* hp = reinterpret_cast<LrPair*>(blob.data() + o_pair);
+    auto* hci = reinterpret_cast<uint32_t*>(blob.data() + o_ci);
+    auto* hpi = reinterpret_cast<uint32_t*>(blob.data() + o_pi);
+    for (uint32_t i = 0; i < R; ++i) {
+        if (!one_list(reads[i].list, reads[i].n))
+            return fail(ctx, LASPJ_E_INVAL, "list_reads: read %u's list", i);
+        const LV v = view(reads[i].list);
+        hr[i] = LwDesc{v.key, v.tok, v.toff, reads[i].n, reads[i].strict ? 1u : 0u};
+    }
+    uint64_t slots = 0, citems = 0, pitems = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        if (!one_list(curs[c].list, curs[c].n))
+            return fail(ctx, LASPJ_E_INVAL, "list_reads: current %u's list", c);
+        const LV v = view(curs[c].list);
+        const uint32_t hsize = pow2_at_least(2ull * std::max(curs[c].n, 1u));
+        hc[c] = LrCur{v.key, v.tok, v.toff, v.hdr, curs[c].n, v.ct, (uint32_t)slots, hsize};
+        hci[c] = (uint32_t)citems;
+        slots += hsize;
+        citems += (curs[c].n + 255) / 256;
+        if (slots > 0x7FFFFFFFull) return fail(ctx, LASPJ_E_RANGE, "list_reads: lists too long");
+    }
+    hci[C] = (uint32_t)citems;
+    for (uint32_t k = 0; k < P; ++k) {
+        if (pairs[k].read >= R || pairs[k].cur >= C)
+            return fail(ctx, LASPJ_E_INVAL, "list_reads: pair %u", k);
+        hp[k] = LrPair{pairs[k].read, pairs[k].cur};
+        hpi[k] = (uint32_t)pitems;
+        pitems += (reads[pairs[k].read].n + kLwTile - 1) / kLwTile;
+        if (pitems > 0x7FFFFFFFull)
+            return fail(ctx, LASPJ_E_RANGE, "list_reads: thresholds too long");
+    }
+    hpi[P] = (uint32_t)pitems;
+    LGuard g(ctx);
+    // device: [table keys 8 slots | first indices 4 slots | flags 4 P | error word], zeroed (to
+    // a multiple of 256 bytes), then room for the descriptors
+    const uint64_t o_hi = 8ull * slots, o_fl = o_hi + 4ull * slots, o_err = o_fl + 4ull * P;
+    const uint64_t zbytes = (o_err + 4 + 255) & ~255ull;
+    if (int s = grow_block(ctx, &ctx->lw_dev, &ctx->lw_dev_bytes,
+                           zbytes + ((dbytes + 255) & ~255ull), false, what))
+        return s;
+    if (int s = lw_answers(ctx, lw_err_at(P) + 4, what)) return s;
+    char* base = static_cast<char*>(ctx->lw_dev);
+    const char* ddev = nullptr;
+    if (const void* slot = laspj::stage_small(ctx, blob.data(), dbytes))
+        ddev = static_cast<const char*>(laspj::staged_dev(ctx, slot));
+    if (!ddev) {
+        // too many for the ring: copied behind the zeroed block, and landed before `blob` goes
+        LJ_HIP(ctx, hipMemcpyAsync(base + zbytes, blob.data(), dbytes, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ddev = base + zbytes;
+    }
+    LJ_HIP(ctx, hipMemsetAsync(base, 0, zbytes, ctx->stream));
+    LrPass p;
+    p.rd = reinterpret_cast<const LwDesc*>(ddev);
+    p.cur = reinterpret_cast<const LrCur*>(ddev + o_cur);
+    p.pair = reinterpret_cast<const LrPair*>(ddev + o_pair);
+    p.citem0 = reinterpret_cast<const uint32_t*>(ddev + o_ci);
+    p.pitem0 = reinterpret_cast<const uint32_t*>(ddev + o_pi);
+    p.C = C;
+    p.P = P;
+    p.hk = reinterpret_cast<u64*>(base);
+    p.hi = reinterpret_cast<uint32_t*>(base + o_hi);
+    p.flags = reinterpret_cast<uint32_t*>(base + o_fl);
+    p.met = static_cast<uint8_t*>(ctx->lw_hd);
+    p.err_out = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->lw_hd) + lw_err_at(P));
+    rk.flag = reinterpret_cast<uint32_t*>(base + o_err);
+    if (citems)
+        hipLaunchKernelGGL(k_lr_insert, dim3((unsigned)citems), dim3(256), 0, ctx->stream, rk, p);
+    if (pitems)
+        hipLaunchKernelGGL(k_lr_check, dim3((unsigned)pitems), dim3(kLwTile), 0, ctx->stream, rk,
+                           p);
+    hipLaunchKernelGGL(k_lr_finish, dim3(1), dim3(256), 0, ctx->stream, rk, p);
+    LJ_LAUNCHED(ctx);
+    LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return list_waiters_answer(ctx, P, met, what);
 }
 
 }  // namespace laspj

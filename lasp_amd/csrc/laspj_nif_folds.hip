@@ -466,7 +466,10 @@ int fold_run_locked(laspj_ctx* ctx, NifState* S, laspj_fold* f, int32_t* status,
                 return fail(ctx, LASPJ_E_DEVICE, "fold_run: %u tokens stay unmapped", S->lv_ans[4]);
             continue;
         }
-        if (st == 1) std::swap(out->list, out->dst);
+        if (st == 1) {
+            std::swap(out->list, out->dst);
+            laspj::llazy_clear(out);                            // write/4: a fresh #dv
+        }
         *status = st;
         return LASPJ_OK;
     }

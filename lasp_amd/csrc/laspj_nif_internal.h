@@ -107,6 +107,9 @@ struct LWaiter {
     uint32_t n = 0;                  // the threshold's entries
     uint64_t epoch = 0;
 };
+// An entry of a list variable's `#dv.lazy_threads` ({threshold, wait, From, Type, Threshold},
+// lasp_core.erl:730-758) is kept the same way, always with strict == 0, and follows the same
+// rules across growth, a dictionary reset and a widening.
 
 }  // namespace laspj
 
@@ -173,6 +176,7 @@ struct laspj_lvar {
     laspj_batch* tmp = nullptr;      // l's list form (the two-step composition, A/B only)
     std::vector<uint8_t> image;
     std::vector<laspj::LWaiter> waiters;   // `#dv.waiting_threads`, in list order
+    std::vector<laspj::LWaiter> lazy;      // `#dv.lazy_threads`, in list order
 };
 
 // One lasp_process running map/6 (lasp_core.erl:641-667) from the OR-Set `in` into the list
@@ -528,6 +532,8 @@ void waiter_cells_drop(NifState* S, laspj_var* c);
 int spill_lvars(NifState* S, KindState& K);
 // a list variable's waiter gives its device list back, its image stays (the context alive)
 void lwaiter_release(LWaiter& w);
+// write/4 builds a fresh #dv (lasp_core.erl:842-843): the list variable's lazy threads go
+void llazy_clear(laspj_lvar* lv);
 // what a call registered in the namespace since `before`: the device images are stale
 struct RegMark {
     uint32_t n = 0;

@@ -4,7 +4,9 @@
 // list kernels are laspj_lists.hip's; the order tables and the producer of intersection/7's
 // OR-Set branch (lasp_core.erl:559-568, 583) are laspj_lvars.hip's.  The variable's waiting
 // threads (read/6 and write/4's reply_to_all, lasp_core.erl:331-364, 765-825) are kept here as
-// device lists and checked by laspj_lists.hip's waiter pass, alone or behind a bind.
+// device lists and checked by laspj_lists.hip's waiter pass, alone or behind a bind; its lazy
+// threads (wait_needed/6, :730-758) likewise, and read/6 / read_any/3 over them (:331-364,
+// 371-420, 795-813) answered by laspj_lists.hip's read pass.
 
 #include "laspj_nif_internal.h"
 
@@ -16,6 +18,11 @@ namespace laspj {
 void lwaiter_release(LWaiter& w) {
     if (w.list) laspj_batch_destroy(w.list);
     w.list = nullptr;
+}
+
+void llazy_clear(laspj_lvar* lv) {
+    for (LWaiter& z : lv->lazy) lwaiter_release(z);
+    lv->lazy.clear();
 }
 
 namespace {
@@ -296,14 +303,16 @@ int lvar_intersection_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj
         out->val->known_e = S->lv_ans[0];
         out->val->known_t = S->lv_ans[1];
     }
+    if (st == LASPJ_BIND_WRITTEN) llazy_clear(out);      // write/4: a fresh #dv (:842-843)
     *status = st;
     return LASPJ_OK;
 }
 
 // an image walked into lv->val over the namespace (its unseen terms registered, the images
 // and tables brought up to them); *ok false: the walk refused it (its registrations undone)
+// into (or null: lv->val): the list that takes the items
 int lvar_walk_val(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, const uint8_t* p, uint64_t n,
-                  bool* ok) {
+                  bool* ok, laspj_batch* into = nullptr) {
     KindState& K = *lv->ns;
     *ok = false;
     if (!K.dict)
@@ -317,20 +326,60 @@ int lvar_walk_val(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, const uint8_t* p,
     if (st != LASPJ_DEC_OK) return LASPJ_OK;
     reg_note(S, K, m);
     if (int s = lvar_prepare(ctx, S, K)) return s;
-    if (int s = lvar_upload(ctx, lv->val, it)) return s;
+    if (int s = lvar_upload(ctx, into ? into : lv->val, it)) return s;
     *ok = true;
     return LASPJ_OK;
 }
 
-// *ok: every waiter's threshold is on the device over the current dictionary.  One whose
-// list a dictionary reset made stale is walked back in from its image here (its terms
-// registered afresh: the caller brings the images and tables up to them); in a wide
-// namespace, or when the walk refuses an image, the lists stay as they are.  S->mu held.
-int lwaiters_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
+// threshold_met(lasp_orset, #dv.value, T) (lasp_lattice.erl:62-75) for the threshold walked
+// into lv->val: is_inflation / is_strict_inflation of it -> the value, one device pass
+int lvar_val_met(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, int strict, uint8_t* met) {
+    const LvOrder ord(ctx, *lv->ns);
+    laspj_buf* res = nullptr;
+    if (int s = laspj_buf_create(ctx, 8, &res)) return s;
+    uint8_t b = 0;
+    int s = laspj_list_inflation(ctx, lv->val, lv->list, strict ? 1 : 0, &ord.o, res);
+    if (s == LASPJ_OK) s = laspj_buf_download(ctx, res, 0, &b, 1);
+    laspj_buf_destroy(res);
+    if (s) return s;
+    ++S->stats[ST_PASSES];
+    *met = b;
+    return LASPJ_OK;
+}
+
+// The threshold walked into *list (lv->val, or a read_any's list of its own) becomes the
+// device list of a new entry {id, strict, image} at the tail of `es` — the variable's waiters
+// (lasp_core.erl:355-364) or its lazy threads (:747-755) — and a fresh block takes its place
+// (fresh false: *list is the caller's to give away, and comes back null).
+int lvar_keep(laspj_ctx* ctx, laspj_lvar* lv, std::vector<LWaiter>& es, laspj_batch** list,
+              bool fresh, uint64_t id, int strict, const uint8_t* image, uint64_t n) {
+    LWaiter w;
+    w.id = id;
+    w.strict = strict ? 1 : 0;
+    w.image.assign(image, image + n);
+    w.n = (*list)->known_e;
+    w.epoch = lv->ns->epoch;
+    es.reserve(es.size() + 1);
+    laspj_batch* next = nullptr;
+    if (fresh)
+        if (int c = laspj_list_batch_create(ctx, LASPJ_KIND_ORSET_LIST, 1, 1, 1, &next)) return c;
+    w.list = *list;
+    *list = next;
+    es.push_back(std::move(w));
+    return LASPJ_OK;
+}
+
+// *ok: every threshold of `es` (the variable's waiters, or its lazy threads) is on the device
+// over the current dictionary.  One whose list a dictionary reset made stale is walked back
+// in from its image here (its terms registered afresh: the caller brings the images and
+// tables up to them); in a wide namespace, or when the walk refuses an image, the lists stay
+// as they are.  S->mu held.
+int lentries_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, std::vector<LWaiter>& es,
+                   bool* ok) {
     KindState& K = *lv->ns;
     *ok = !K.wide;
     if (K.wide) return LASPJ_OK;
-    for (LWaiter& w : lv->waiters) {
+    for (LWaiter& w : es) {
         if (w.list && w.epoch == K.epoch) continue;
         if (!K.dict)
             if (int s = reset_dict(ctx, S, K)) return s;
@@ -353,6 +402,12 @@ int lwaiters_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
         ++S->stats[ST_HYDRATED];
     }
     return LASPJ_OK;
+}
+int lwaiters_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
+    return lentries_ready(ctx, S, lv, lv->waiters, ok);
+}
+int llazy_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
+    return lentries_ready(ctx, S, lv, lv->lazy, ok);
 }
 
 // the waiters as the check pass takes them, in list order
@@ -392,6 +447,7 @@ int spill_lvars(NifState* S, KindState& K) {
         if (int s = lvar_spill(S, lv)) return s;
         // the waiters' lists name the same slots: released, their images kept
         for (LWaiter& w : lv->waiters) lwaiter_release(w);
+        for (LWaiter& z : lv->lazy) lwaiter_release(z);
     }
     return LASPJ_OK;
 }
@@ -422,6 +478,7 @@ void lvar_free_batches(laspj_lvar* lv) {
         *b = nullptr;
     }
     for (laspj::LWaiter& w : lv->waiters) laspj::lwaiter_release(w);
+    for (laspj::LWaiter& z : lv->lazy) laspj::lwaiter_release(z);
 }
 
 }  // namespace
@@ -531,6 +588,7 @@ int laspj_lvar_etf_bind(laspj_lvar* lv, const uint8_t* value, uint64_t n, int32_
         if (!ok) return laspj::fallback(S);
         int32_t st = 0;
         if (int s = laspj::lvar_bind(ctx, S, lv, &st)) return s;
+        if (st == LASPJ_BIND_WRITTEN) laspj::llazy_clear(lv);    // write/4: a fresh #dv
         *status = st;
         *verdict = LASPJ_NIF_OK;
         return LASPJ_OK;
@@ -549,6 +607,7 @@ int laspj_lvar_etf_write(laspj_lvar* lv, const uint8_t* value, uint64_t n, int32
         bool ok = false;
         if (!K.wide)
             if (int s = laspj::lvar_walk_val(ctx, S, lv, value, n, &ok)) return s;
+        laspj::llazy_clear(lv);                          // write/4: a fresh #dv (:842-843)
         if (!ok) {
             // held as its image: read answers it, the other calls FALLBACK until a write
             lv->image.assign(value, value + n);
@@ -646,17 +705,8 @@ int laspj_lvar_etf_threshold(laspj_lvar* lv, const uint8_t* threshold, uint64_t 
         if (ok)
             if (int s = laspj::lvar_walk_val(ctx, S, lv, threshold, n, &ok)) return s;
         if (!ok) return laspj::fallback(S);
-        // threshold_met (lasp_lattice.erl:62-75): is_inflation / is_strict_inflation of the
-        // threshold -> the value
-        const laspj::LvOrder ord(ctx, *lv->ns);
-        laspj_buf* res = nullptr;
-        if (int s = laspj_buf_create(ctx, 8, &res)) return s;
         uint8_t b = 0;
-        int s = laspj_list_inflation(ctx, lv->val, lv->list, strict ? 1 : 0, &ord.o, res);
-        if (s == LASPJ_OK) s = laspj_buf_download(ctx, res, 0, &b, 1);
-        laspj_buf_destroy(res);
-        if (s) return s;
-        ++S->stats[laspj::ST_PASSES];
+        if (int s = laspj::lvar_val_met(ctx, S, lv, strict, &b)) return s;
         *result = b ? 1 : 0;
         *verdict = LASPJ_NIF_OK;
         return LASPJ_OK;
@@ -683,37 +733,18 @@ int laspj_lvar_wait(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int st
             if (int s = laspj::lvar_walk_val(ctx, S, lv, threshold, n, &ok)) return s;
         if (!ok) return laspj::fallback(S);
         // threshold_met (lasp_lattice.erl:62-75) as laspj_lvar_etf_threshold answers it
-        const laspj::LvOrder ord(ctx, *lv->ns);
-        laspj_buf* res = nullptr;
-        if (int s = laspj_buf_create(ctx, 8, &res)) return s;
         uint8_t b = 0;
-        int s = laspj_list_inflation(ctx, lv->val, lv->list, strict ? 1 : 0, &ord.o, res);
-        if (s == LASPJ_OK) s = laspj_buf_download(ctx, res, 0, &b, 1);
-        laspj_buf_destroy(res);
-        if (s) return s;
-        ++S->stats[laspj::ST_PASSES];
-        *verdict = LASPJ_NIF_OK;
+        if (int s = laspj::lvar_val_met(ctx, S, lv, strict, &b)) return s;
         if (b) {
             *met = 1;
+            *verdict = LASPJ_NIF_OK;
             return LASPJ_OK;
         }
         // unmet (lasp_core.erl:355-364): appended to waiting_threads; the walked threshold
         // (lv->val) becomes the waiter's list, a fresh block takes its place
-        laspj::LWaiter w;
-        w.id = id;
-        w.strict = strict ? 1 : 0;
-        w.image.assign(threshold, threshold + n);
-        w.n = lv->val->known_e;
-        w.epoch = lv->ns->epoch;
-        lv->waiters.reserve(lv->waiters.size() + 1);
-        laspj_batch* fresh = nullptr;
-        if (int c = laspj_list_batch_create(ctx, LASPJ_KIND_ORSET_LIST, 1, 1, 1, &fresh)) {
-            *verdict = LASPJ_NIF_FALLBACK;
+        if (int c = laspj::lvar_keep(ctx, lv, lv->waiters, &lv->val, true, id, strict, threshold, n))
             return c;
-        }
-        w.list = lv->val;
-        lv->val = fresh;
-        lv->waiters.push_back(std::move(w));
+        *verdict = LASPJ_NIF_OK;
         return LASPJ_OK;
     });
 }
@@ -833,6 +864,272 @@ int laspj_lvar_waiter_at(laspj_lvar* lv, uint32_t k, uint64_t* id, int32_t* stri
     *strict = lv->waiters[k].strict;
     *threshold = lv->waiters[k].image.data();
     *n = lv->waiters[k].image.size();
+    return LASPJ_OK;
+}
+
+int laspj_lvar_wait_needed(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict,
+                           uint64_t id, int32_t* needed, int32_t* verdict) {
+    const laspj::Entry e = enter_lvar(lv, "lvar_wait_needed", threshold && n && needed && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    ++S->stats[laspj::ST_CALLS];
+    *needed = 0;
+    *verdict = LASPJ_NIF_FALLBACK;
+    return laspj::nomem_guard(ctx, "lvar_wait_needed", [&]() -> int {
+        bool ok = false, wok = false;
+        if (int s = laspj::lvar_ready(ctx, S, lv, &ok)) return s;
+        // (stale waiters and lazy threads come back ahead of the threshold's walk, as in
+        // laspj_lvar_wait; one the walk refuses waits for the call that checks it)
+        if (ok)
+            if (int s = laspj::lwaiters_ready(ctx, S, lv, &wok)) return s;
+        if (ok)
+            if (int s = laspj::llazy_ready(ctx, S, lv, &wok)) return s;
+        if (ok)
+            if (int s = laspj::lvar_walk_val(ctx, S, lv, threshold, n, &ok)) return s;
+        if (!ok) return laspj::fallback(S);
+        uint8_t b = 0;
+        if (int s = laspj::lvar_val_met(ctx, S, lv, strict, &b)) return s;
+        // met (lasp_core.erl:735-737), or somebody is reading already (:739-741)
+        if (b || !lv->waiters.empty()) {
+            *needed = 1;
+            *verdict = LASPJ_NIF_OK;
+            return LASPJ_OK;
+        }
+        // the stored {strict, T} would later be handed to keyfind as a value (:798)
+        if (strict) return laspj::fallback(S);
+        // :747-755: appended to lazy_threads; lv->val becomes the entry's list
+        if (int c = laspj::lvar_keep(ctx, lv, lv->lazy, &lv->val, true, id, 0, threshold, n))
+            return c;
+        *verdict = LASPJ_NIF_OK;
+        return LASPJ_OK;
+    });
+}
+
+namespace {
+
+// a read_any's own threshold lists, destroyed unless a waiter took them
+struct OwnLists {
+    std::vector<laspj_batch*> v;
+    ~OwnLists() {
+        for (laspj_batch* b : v)
+            if (b) laspj_batch_destroy(b);
+    }
+};
+
+// laspj_lvar_read (n = 1, the threshold walked into lvs[0]->val) and laspj_lvar_read_any (a
+// list of its own per read) with S->mu held and the handles checked
+int lreads_locked(laspj_ctx* ctx, laspj::NifState* S, uint32_t n, laspj_lvar* const* lvs,
+                  const uint8_t* const* thresholds, const uint64_t* lens, const int32_t* strict,
+                  bool own, uint64_t id, int32_t* found, uint64_t* lazy_ids, uint32_t cap,
+                  uint32_t* nlazy, int32_t* verdict) {
+    using namespace laspj;
+    // the distinct variables, in the order named
+    std::vector<laspj_lvar*> vars;
+    std::vector<uint32_t> var_of(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const auto at = std::find(vars.begin(), vars.end(), lvs[i]);
+        var_of[i] = (uint32_t)(at - vars.begin());
+        if (at == vars.end()) vars.push_back(lvs[i]);
+    }
+    // values, waiters and lazy threads on the device first, then the thresholds' walks, which
+    // bring the images and tables up to every term registered
+    for (laspj_lvar* lv : vars) {
+        bool ok = false, wok = false;
+        if (int s = lvar_ready(ctx, S, lv, &ok)) return s;
+        if (!ok) return fallback(S);
+        if (int s = lwaiters_ready(ctx, S, lv, &wok)) return s;
+        if (int s = llazy_ready(ctx, S, lv, &ok)) return s;
+        if (!ok) return fallback(S);       // a stale lazy entry whose image the walk refuses
+    }
+    OwnLists mine;
+    std::vector<ListWaiter> reads(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        laspj_lvar* lv = lvs[i];
+        laspj_batch* into = nullptr;
+        if (own) {
+            mine.v.push_back(nullptr);
+            if (int s = laspj_list_batch_create(ctx, LASPJ_KIND_ORSET_LIST, 1, 1, 1, &mine.v.back()))
+                return s;
+            into = mine.v.back();
+        }
+        bool ok = false;
+        if (int s = lvar_walk_val(ctx, S, lv, thresholds[i], lens[i], &ok, into)) return s;
+        if (!ok) return fallback(S);
+        const laspj_batch* t = into ? into : lv->val;
+        reads[i] = ListWaiter{t, t->known_e, strict[i] ? 1u : 0u};
+    }
+    for (laspj_lvar* lv : vars) {
+        const KindState& K = *lv->ns;
+        if (K.wide || !lv->resident || lv->epoch != K.epoch) return fallback(S);
+        for (const LWaiter& z : lv->lazy)
+            if (!z.list || z.epoch != K.epoch) return fallback(S);
+    }
+    // read i's pairs: its variable's value, then that variable's lazy thresholds in list
+    // order; one pass per namespace named (its order tables are the pass's)
+    std::vector<uint32_t> nl(vars.size()), pair0(n + 1, 0);
+    for (size_t v = 0; v < vars.size(); ++v) nl[v] = (uint32_t)vars[v]->lazy.size();
+    for (uint32_t i = 0; i < n; ++i) pair0[i + 1] = pair0[i] + 1 + nl[var_of[i]];
+    std::vector<uint8_t> met(pair0[n], 0);
+    std::vector<uint8_t> done(n, 0);
+    for (uint32_t first = 0; first < n; ++first) {
+        if (done[first]) continue;
+        KindState& K = *lvs[first]->ns;
+        std::vector<ListWaiter> rd;
+        std::vector<ListReadCur> curs;
+        std::vector<ListReadPair> pairs;
+        std::vector<uint32_t> cur0(vars.size(), ~0u), where;
+        for (uint32_t i = first; i < n; ++i) {
+            if (done[i] || lvs[i]->ns.get() != &K) continue;
+            done[i] = 1;
+            const uint32_t v = var_of[i];
+            if (cur0[v] == ~0u) {
+                cur0[v] = (uint32_t)curs.size();
+                curs.push_back(ListReadCur{vars[v]->list, vars[v]->list->known_e});
+                for (const LWaiter& z : vars[v]->lazy) curs.push_back(ListReadCur{z.list, z.n});
+            }
+            for (uint32_t c = 0; c <= nl[v]; ++c) {
+                pairs.push_back(ListReadPair{(uint32_t)rd.size(), cur0[v] + c});
+                where.push_back(pair0[i] + c);
+            }
+            rd.push_back(reads[i]);
+        }
+        std::vector<uint8_t> got(pairs.size(), 0);
+        const LvOrder ord(ctx, K);
+        const uint64_t t0 = now_ns();
+        if (int s = list_reads_check(ctx, &ord.o, rd.data(), (uint32_t)rd.size(), curs.data(),
+                                     (uint32_t)curs.size(), pairs.data(), (uint32_t)pairs.size(),
+                                     got.data()))
+            return s;
+        ++S->stats[ST_PASSES];
+        S->stats[ST_NS_WAIT] += now_ns() - t0;
+        for (size_t k = 0; k < got.size(); ++k) met[where[k]] = got[k];
+    }
+    // the fold of :372-414 over the met bytes (laspj_reads_host.cpp)
+    std::vector<const uint8_t*> ans(n);
+    for (uint32_t i = 0; i < n; ++i) ans[i] = met.data() + pair0[i];
+    ReadFold F;
+    read_fold(n, var_of.data(), (uint32_t)vars.size(), nl.data(), ans.data(), &F);
+    *verdict = LASPJ_NIF_OK;
+    *found = F.found;
+    for (uint32_t i = 0; i < n; ++i) nlazy[i] = (uint32_t)F.fired[i].size();
+    if (F.total > cap) return LASPJ_OK;                  // nothing is changed
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t j : F.fired[i]) lazy_ids[at++] = lvs[i]->lazy[j].id;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!F.blocked[i]) continue;
+        // unmet (:355-364): the waiter laspj_lvar_wait makes, its list the walked threshold
+        laspj_lvar* lv = lvs[i];
+        laspj_batch** list = own ? &mine.v[i] : &lv->val;
+        if (int c = lvar_keep(ctx, lv, lv->waiters, list, !own, id, strict[i], thresholds[i],
+                              lens[i]))
+            return c;
+    }
+    for (size_t v = 0; v < vars.size(); ++v) {
+        std::vector<LWaiter>& lz = vars[v]->lazy;
+        if (F.still[v].size() == lz.size()) continue;
+        std::vector<LWaiter> keep;
+        keep.reserve(F.still[v].size());
+        std::vector<uint8_t> stays(lz.size(), 0);
+        for (uint32_t j : F.still[v]) stays[j] = 1;
+        for (size_t j = 0; j < lz.size(); ++j) {
+            if (stays[j]) keep.push_back(std::move(lz[j]));
+            else lwaiter_release(lz[j]);
+        }
+        lz.swap(keep);
+    }
+    return LASPJ_OK;
+}
+
+}  // namespace
+
+int laspj_lvar_read(laspj_lvar* lv, const uint8_t* threshold, uint64_t n, int strict, uint64_t id,
+                    int32_t* met, uint64_t* lazy_ids, uint32_t cap, uint32_t* nlazy,
+                    uint32_t* nstill_lazy, int32_t* verdict) {
+    const laspj::Entry e = enter_lvar(lv, "lvar_read", threshold && n && met && (lazy_ids || !cap) &&
+                                                           nlazy && nstill_lazy && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    ++S->stats[laspj::ST_CALLS];
+    *met = 0;
+    *nlazy = 0;
+    *nstill_lazy = (uint32_t)lv->lazy.size();
+    *verdict = LASPJ_NIF_FALLBACK;
+    return laspj::nomem_guard(ctx, "lvar_read", [&]() -> int {
+        int32_t found = -1;
+        const int32_t st = strict ? 1 : 0;
+        const int s = lreads_locked(ctx, S, 1, &lv, &threshold, &n, &st, false, id, &found,
+                                    lazy_ids, cap, nlazy, verdict);
+        *met = found == 0 ? 1 : 0;
+        *nstill_lazy = (uint32_t)lv->lazy.size();
+        return s;
+    });
+}
+
+int laspj_lvar_read_any(laspj_ctx* ctx, uint32_t n, laspj_lvar* const* lvs,
+                        const uint8_t* const* thresholds, const uint64_t* lens,
+                        const int32_t* strict, uint64_t id, int32_t* found, uint64_t* lazy_ids,
+                        uint32_t cap, uint32_t* nlazy, int32_t* verdict) {
+    if (!ctx) return LASPJ_E_INVAL;
+    if (!found || !verdict) return fail(ctx, LASPJ_E_INVAL, "lvar_read_any: null argument");
+    *found = -1;
+    *verdict = LASPJ_NIF_OK;
+    if (!n) return LASPJ_OK;                      // lists:foldl over []: not_available_yet
+    if (!lvs || !thresholds || !lens || !strict || (!lazy_ids && cap) || !nlazy)
+        return fail(ctx, LASPJ_E_INVAL, "lvar_read_any: null array");
+    const laspj::Entry e = laspj::enter_ctx(ctx);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    for (uint32_t i = 0; i < n; ++i) {
+        nlazy[i] = 0;
+        if (!lvs[i] || lvs[i]->ctx != ctx || !lvar_alive(S, lvs[i]))
+            return fail(ctx, LASPJ_E_INVAL, "lvar_read_any: variable %u is not this context's", i);
+        if (!thresholds[i] || !lens[i])
+            return fail(ctx, LASPJ_E_INVAL, "lvar_read_any: null threshold");
+    }
+    ++S->stats[laspj::ST_CALLS];
+    *verdict = LASPJ_NIF_FALLBACK;
+    return laspj::nomem_guard(ctx, "lvar_read_any", [&]() -> int {
+        return lreads_locked(ctx, S, n, lvs, thresholds, lens, strict, true, id, found, lazy_ids,
+                             cap, nlazy, verdict);
+    });
+}
+
+int laspj_lvar_lazy_count(const laspj_lvar* lv, uint32_t* n) {
+    laspj::NifState* S = lvar_state(const_cast<laspj_lvar*>(lv));
+    if (!S || !n) return LASPJ_E_INVAL;
+    std::lock_guard<std::mutex> lk(S->mu);
+    *n = (uint32_t)lv->lazy.size();
+    return LASPJ_OK;
+}
+
+int laspj_lvar_lazy_at(laspj_lvar* lv, uint32_t k, uint64_t* id, const uint8_t** threshold,
+                       uint64_t* n) {
+    const laspj::Entry e = laspj::enter(lvar_state(lv), lv ? lv->ctx : nullptr, "lvar_lazy_at",
+                                        id && threshold && n);
+    if (e.rc) return e.rc;
+    if (k >= lv->lazy.size())
+        return fail(e.ctx, LASPJ_E_RANGE, "lvar_lazy_at: no lazy thread %u", k);
+    *id = lv->lazy[k].id;
+    *threshold = lv->lazy[k].image.data();
+    *n = lv->lazy[k].image.size();
+    return LASPJ_OK;
+}
+
+int laspj_lvar_lazy_cancel(laspj_lvar* lv, uint64_t id, int32_t* found) {
+    const laspj::Entry e = enter_lvar(lv, "lvar_lazy_cancel", found != nullptr);
+    if (e.rc) return e.rc;
+    *found = 0;
+    std::vector<laspj::LWaiter>& zs = lv->lazy;
+    for (size_t k = 0; k < zs.size(); ++k)
+        if (zs[k].id == id) {
+            laspj::lwaiter_release(zs[k]);
+            zs.erase(zs.begin() + (ptrdiff_t)k);
+            *found = 1;
+            break;
+        }
     return LASPJ_OK;
 }
 

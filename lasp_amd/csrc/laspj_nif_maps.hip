@@ -399,7 +399,10 @@ int map_run_locked(laspj_ctx* ctx, NifState* S, laspj_map* m, int32_t* status, u
                 return fail(ctx, LASPJ_E_DEVICE, "map_run: %u tokens stay unmapped", S->lv_ans[4]);
             continue;
         }
-        if (st == 1) std::swap(out->list, out->dst);
+        if (st == 1) {
+            std::swap(out->list, out->dst);
+            laspj::llazy_clear(out);                            // write/4: a fresh #dv
+        }
         *status = st;
         return LASPJ_OK;
     }

@@ -628,9 +628,26 @@ class NifListVar:
         check(fn(self.h, C.byref(out), C.byref(olen), C.byref(verd)), self.ctx.h)
         return int(verd.value), (C.string_at(out, olen.value) if verd.value == 0 else None)
 
-    def read(self):
-        """(verdict, the value's image)."""
-        return self._image(self.L.laspj_lvar_etf_read)
+    def read(self, threshold: bytes = None, strict: bool = False, id: int = 0, cap: int = 16):
+        """Without a threshold: (verdict, the value's image) (laspj_lvar_etf_read).  With one:
+        read/6 with the lazy threads' walk (laspj_lvar_read): (met, [lazy ids fired, in list
+        order]) — an unmet threshold is registered as a waiter {id, strict, threshold} and
+        the fired lazy entries leave; met is None on NIF_FALLBACK.  Asks again with more
+        room when more than cap fired (nothing was changed by the first call)."""
+        if threshold is None:
+            return self._image(self.L.laspj_lvar_etf_read)
+        img = bytes(threshold)
+        while True:
+            ids = (C.c_uint64 * max(cap, 1))()
+            met, verd, nl, still = C.c_int32(), C.c_int32(), C.c_uint32(), C.c_uint32()
+            check(self.L.laspj_lvar_read(self.h, img, len(img), int(strict), id, C.byref(met),
+                                         ids, cap, C.byref(nl), C.byref(still), C.byref(verd)),
+                  self.ctx.h)
+            if verd.value != 0:
+                return None, []
+            if nl.value <= cap:
+                return bool(met.value), [int(x) for x in ids[:nl.value]]
+            cap = nl.value
 
     def value(self):
         """(verdict, the image of lasp_orset:value/1 on the list)."""
@@ -697,6 +714,33 @@ class NifListVar:
             out.append((int(wid.value), bool(strict.value), C.string_at(p, ln.value)))
         return out
 
+    def wait_needed(self, img: bytes, strict: bool = False, id: int = 0):
+        """wait_needed/6 (laspj_lvar_wait_needed): needed — True: reply at once (the threshold
+        is met, or somebody is reading already); False: registered as the lazy thread {id,
+        img}; None on NIF_FALLBACK."""
+        needed, verd = C.c_int32(), C.c_int32()
+        img = bytes(img)
+        check(self.L.laspj_lvar_wait_needed(self.h, img, len(img), int(strict), id,
+                                            C.byref(needed), C.byref(verd)), self.ctx.h)
+        return bool(needed.value) if verd.value == 0 else None
+
+    def lazy(self):
+        """[(id, threshold image)] of `#dv.lazy_threads`, in list order."""
+        n = C.c_uint32()
+        check(self.L.laspj_lvar_lazy_count(self.h, C.byref(n)), self.ctx.h)
+        out = []
+        for k in range(n.value):
+            wid, p, ln = C.c_uint64(), C.c_void_p(), C.c_uint64()
+            check(self.L.laspj_lvar_lazy_at(self.h, k, C.byref(wid), C.byref(p), C.byref(ln)),
+                  self.ctx.h)
+            out.append((int(wid.value), C.string_at(p, ln.value)))
+        return out
+
+    def lazy_cancel(self, id: int) -> bool:
+        found = C.c_int32()
+        check(self.L.laspj_lvar_lazy_cancel(self.h, id, C.byref(found)), self.ctx.h)
+        return bool(found.value)
+
     def counts(self):
         """(entries, tokens) of the resident list."""
         ne, nt = C.c_uint32(), C.c_uint32()
@@ -719,6 +763,37 @@ class NifListVar:
             self.close()
         except Exception:
             pass
+
+
+def list_read_any(reads, id: int = 0, cap: int = 16):
+    """read_any/3 (laspj_lvar_read_any) over (NifListVar, threshold image, strict) triples of
+    one context: (found, [[lazy ids fired] per read]), shaped like read_any."""
+    n = len(reads)
+    if n == 0:
+        return -1, []
+    ctx = reads[0][0].ctx
+    keep = [bytes(img) for _v, img, _s in reads]
+    vs = (C.c_void_p * n)(*[v.h.value for v, _i, _s in reads])
+    pv = (C.c_char_p * n)(*keep)
+    nv = (C.c_uint64 * n)(*[len(x) for x in keep])
+    st = (C.c_int32 * n)(*[int(bool(s)) for _v, _i, s in reads])
+    while True:
+        ids = (C.c_uint64 * max(cap, 1))()
+        nl = (C.c_uint32 * n)()
+        found, verd = C.c_int32(), C.c_int32()
+        check(ctx.L.laspj_lvar_read_any(ctx.h, n, vs, pv, nv, st, id, C.byref(found), ids, cap,
+                                        nl, C.byref(verd)), ctx.h)
+        if verd.value != 0:
+            return None, []
+        total = sum(int(x) for x in nl)
+        if total <= cap:
+            break
+        cap = total
+    out, at = [], 0
+    for k in range(n):
+        out.append([int(x) for x in ids[at:at + nl[k]]])
+        at += nl[k]
+    return int(found.value), out
 
 
 class NifMap:
