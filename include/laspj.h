@@ -1256,7 +1256,9 @@ int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found);
  * on the device from the namespace's images (krank from the element order; grank[64 e + k] =
  * k's place among element e's tokens: tokens are only compared within one key's runs), fully
  * after a rebuild of the images and for the patched element slots otherwise.  Keys that are
- * pairs (product outputs) are not taken.  A dictionary reset (laspj_nif_reset, the 2^20 cap)
+ * pairs (product outputs) are taken by a pair-keyed variable only (laspj_lvar_create_pairs,
+ * "pair-keyed list variables" below); a variable made by laspj_lvar_create refuses them as it
+ * refuses any image its walk does not take.  A dictionary reset (laspj_nif_reset, the 2^20 cap)
  * or a namespace going wide writes the list out to its image first; after a reset it is
  * walked back in at its next call, in a wide namespace it stays host-held (read answers the
  * image, the other calls FALLBACK).  Its `#dv.waiting_threads` are kept beside it
@@ -1266,8 +1268,9 @@ int laspj_var_lazy_cancel(laspj_var* var, uint64_t id, int32_t* found);
  * are kept the same way (laspj_lvar_wait_needed and the calls after it): a lazy threshold is a
  * device list of its own too, and a read checks the value and every lazy threshold against
  * its own threshold in one device pass.  Every call that answers LASPJ_BIND_WRITTEN on a list
- * variable (laspj_lvar_intersection, laspj_lvar_intersection_recheck, laspj_lvar_etf_bind,
- * laspj_map_run, laspj_fold_run) and laspj_lvar_etf_write empty its lazy list (write/4 builds
+ * variable (laspj_lvar_intersection, laspj_lvar_intersection_recheck, laspj_lvar_product,
+ * laspj_lvar_product_recheck, laspj_lvar_etf_bind, laspj_map_run, laspj_fold_run) and
+ * laspj_lvar_etf_write empty its lazy list (write/4 builds
  * a fresh #dv, lasp_core.erl:842-843); LASPJ_BIND_NOOP and LASPJ_BIND_REFUSED leave it alone.
  * Every call takes the context's call lock, never the group-commit queue.
  * After the context is gone every call answers LASPJ_E_INVAL and destroy still frees. */
@@ -1280,6 +1283,28 @@ typedef struct laspj_lvar laspj_lvar;
  * `peer`'s context and namespace; peer must be LASPJ_KIND_ORSET (LASPJ_E_KIND otherwise).
  * The namespace is shared-owned: peer may be destroyed first. */
 int laspj_lvar_create(laspj_var* peer, laspj_lvar** out);
+/* Pair-keyed list variables: declare/3 (lasp_core.erl:208-218) of the variable product/7
+ * (lasp_core.erl:499-533) binds into.  As laspj_lvar_create, but the variable is pair-keyed
+ * for its whole life: every image of it — another node's state (laspj_lvar_etf_bind), a
+ * written value (laspj_lvar_etf_write), the thresholds of laspj_lvar_etf_threshold,
+ * laspj_lvar_wait, laspj_lvar_wait_needed, laspj_lvar_read and laspj_lvar_read_any (each
+ * variable's threshold in that variable's mode), and its own image after a dictionary reset —
+ * is walked in pair mode.  The walk takes [{{X, Y}, [{[Tx, Ty], Bool}]}]: the key a 2-tuple
+ * whose X and Y join the namespace as elements; each token a proper 2-element list (LIST_EXT
+ * of two with a NIL tail, or STRING_EXT of two) whose Tx is registered as a token of X and Ty
+ * as a token of Y.  Items: key LASPJ_LIST_PAIR | x << 31 | y, token LASPJ_LIST_COMPOUND |
+ * gx << 31 | gy | flag (g = 64 e + k).  The namespace's rank tables serve as they are: inside
+ * one key {X, Y} every Tx is X's and every Ty is Y's, so comparing element-wise by krank and
+ * by a token's place inside its element is term order.  Anything else is refused as the plain
+ * walk refuses (the registrations made so far undone; bind, threshold and wait answer verdict
+ * FALLBACK, a write holds the value as its image): a key that is no 2-tuple, a token that is
+ * no 2-list, an element past 64 distinct tokens, `==`-equal terms under two images, improper
+ * lists.  Every laspj_lvar_* call keeps its contract on such a variable, except:
+ * laspj_lvar_intersection and laspj_lvar_intersection_recheck into it answer verdict FALLBACK
+ * (the variable unchanged), laspj_map_create and laspj_fold_create with it as `out` answer
+ * LASPJ_E_KIND, and laspj_lvar_product binds into no other kind of variable.  Nested pairs
+ * (a product of product outputs) are not expressed. */
+int laspj_lvar_create_pairs(laspj_var* peer, laspj_lvar** out);
 /* the `#dv` (include/lasp.hrl:60-63) is dropped: its lists are released, and the namespace
  * with them when this was its last holder */
 int laspj_lvar_destroy(laspj_lvar* lv);
@@ -1356,6 +1381,30 @@ int laspj_lvar_recheck(laspj_lvar* lv, uint64_t* ids, uint32_t cap, uint32_t* nm
 int laspj_lvar_intersection_recheck(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
                                     uint64_t* ids, uint32_t cap, uint32_t* nmet,
                                     uint32_t* nwaiting, int32_t* verdict);
+/* lasp_core:product/7's OR-Set branch (lasp_core.erl:499-533, with
+ * lasp_lattice:orset_causal_product/2, lasp_lattice.erl:303-308) re-run over resident
+ * variables: for each entry {X, Cx} of l and each {Y, Cy} of r in term order (cells holding
+ * any token, tombstoned or not) the entry {{X, Y}, [{[Tx, Ty], XDeleted orelse YDeleted}]},
+ * l-major, both token runs reversed as the double foldl leaves them; then bind/3 (:291-312)
+ * of that AccValue into the pair-keyed out: *status LASPJ_BIND_NOOP, LASPJ_BIND_WRITTEN or
+ * LASPJ_BIND_REFUSED.  A side pass compacts both inputs' cells; the host reads the four
+ * totals (held elements and tokens per side: the one small synchronisation the sizes cost,
+ * |L| x |R| has no useful bound beforehand) and sizes the output; the write pass places
+ * every entry and token by a closed form of the two sides' prefixes, without a scan; the
+ * general list bind follows (pair keys have no rank universe).  l == r is allowed.  An empty
+ * side gives AccValue [] and bind/3 decides.  More than 0xFFFFFFF0 entries or tokens:
+ * LASPJ_E_RANGE before anything of that size is allocated; a failed allocation:
+ * LASPJ_E_NOMEM; out unchanged in both.  verdict FALLBACK, out exactly as it was:
+ * laspj_lvar_intersection's cases, and an out that is not pair-keyed. */
+int laspj_lvar_product(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                       int32_t* verdict);
+/* laspj_lvar_product (lasp_core.erl:499-533, 291-312) and, when it answers
+ * LASPJ_BIND_WRITTEN, laspj_lvar_recheck(out) (lasp_core.erl:765-825) in one call, with
+ * laspj_lvar_intersection_recheck's contract: the waiters are checked against the merge
+ * inside the bind's synchronisation. */
+int laspj_lvar_product_recheck(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                               uint64_t* ids, uint32_t cap, uint32_t* nmet, uint32_t* nwaiting,
+                               int32_t* verdict);
 /* a waiter leaves before it was met (its process died, or the NIF's own walk replied to it:
  * the first waiter with that id of `#dv.waiting_threads`, include/lasp.hrl:60-63); *found 0
  * when there is none */

@@ -257,7 +257,11 @@ SIGNATURES = {
     "laspj_filter_results": (i, [vp, vp, u64]),
     "laspj_var_intersection": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_lvar_create": (i, [vp, vpp]),
+    "laspj_lvar_create_pairs": (i, [vp, vpp]),
     "laspj_lvar_destroy": (i, [vp]),
+    "laspj_lvar_product": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "laspj_lvar_product_recheck": (i, [vp, vp, vp, C.POINTER(C.c_int32), vp, u32,
+                                       C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int32)]),
     "laspj_lvar_intersection": (i, [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_lvar_etf_bind": (i, [vp, vp, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "laspj_lvar_etf_write": (i, [vp, vp, u64, C.POINTER(C.c_int32)]),

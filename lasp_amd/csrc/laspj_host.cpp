@@ -1302,6 +1302,97 @@ int list_walk(laspj_dict* dict, int32_t kind, const uint8_t* p, size_t n, ListIt
     return st;
 }
 
+// product/7's output (lasp_core.erl:499-533, lasp_lattice.erl:303-308) as another node sends
+// it: [{{X, Y}, [{[Tx, Ty], Bool}]}].  X and Y are elements of the namespace, Tx a token of X
+// and Ty a token of Y, so the items compare element-wise by the tables the slots have.
+int list_walk_pairs(laspj_dict* dict, const uint8_t* p, size_t n, ListItems* it) {
+    Dict* d = &dict->d;
+    it->keys.clear();
+    it->toff.assign(1, 0);
+    it->toks.clear();
+    d->journal.clear();
+    int st = LASPJ_DEC_OK;
+    // one half of a pair token registered under its element: the token item's g = 64 e + k
+    auto half = [&](uint32_t e, const uint8_t* t, size_t tl, uint64_t* g) {
+        uint16_t ts = 0;
+        if (!tl) return (int)LASPJ_DEC_MALFORMED;
+        if (int s = reg_tok(d, e, t, tl, &ts)) return s;
+        *g = 64ull * e + ts;
+        return *g > 0x7FFFFFFFull ? (int)LASPJ_DEC_UNREPRESENTABLE : (int)LASPJ_DEC_OK;
+    };
+    try {
+        const uint8_t* t;
+        size_t tn;
+        st = payload_term(p, n, -1, -1, &t, &tn);
+        if (st == LASPJ_DEC_OK && t[0] != kNil && t[0] != kList) st = LASPJ_DEC_MALFORMED;
+        if (st == LASPJ_DEC_OK && t[0] != kNil) {
+            ListIt li(t, tn);
+            size_t el;
+            while (st == LASPJ_DEC_OK) {
+                const uint8_t* e = li.next(&el);
+                if (!e) break;
+                // {{X, Y}, [{[Tx, Ty], Bool}, ...]}
+                if (el < 4 || e[0] != kSmallTuple || e[1] != 2 || e[2] != kSmallTuple || e[3] != 2) {
+                    st = LASPJ_DEC_MALFORMED;
+                    break;
+                }
+                const size_t kl = term_len(e + 2, el - 2);
+                if (kl < 4) { st = LASPJ_DEC_MALFORMED; break; }
+                const size_t xl = term_len(e + 4, kl - 2);
+                if (!xl || xl >= kl - 2) { st = LASPJ_DEC_MALFORMED; break; }
+                const size_t yl = term_len(e + 4 + xl, kl - 2 - xl);
+                if (!yl || 2 + xl + yl != kl) { st = LASPJ_DEC_MALFORMED; break; }
+                uint32_t x = 0, y = 0;
+                if ((st = reg_elem(d, e + 4, xl, &x))) break;
+                if ((st = reg_elem(d, e + 4 + xl, yl, &y))) break;
+                const uint8_t* c = e + 2 + kl;
+                const size_t cl = el - 2 - kl;
+                if (!cl || (c[0] != kNil && c[0] != kList)) { st = LASPJ_DEC_MALFORMED; break; }
+                if (c[0] == kList) {
+                    ListIt ci(c, cl);
+                    size_t rl;
+                    while (const uint8_t* r = ci.next(&rl)) {
+                        if (rl < 2 || r[0] != kSmallTuple || r[1] != 2) { st = LASPJ_DEC_MALFORMED; break; }
+                        const size_t tl = term_len(r + 2, rl - 2);
+                        if (!tl) { st = LASPJ_DEC_MALFORMED; break; }
+                        const int flag = bool_atom(r + 2 + tl);
+                        if (flag < 0 || term_len(r + 2 + tl, rl - 2 - tl) != rl - 2 - tl) {
+                            st = LASPJ_DEC_MALFORMED;
+                            break;
+                        }
+                        // the token: a proper list of two terms
+                        const uint8_t* k = r + 2;
+                        const bool two = (k[0] == kList && tl >= 5 && be32(k + 1) == 2) ||
+                                         (k[0] == kString && tl == 5 && be16(k + 1) == 2);
+                        if (!two) { st = LASPJ_DEC_MALFORMED; break; }
+                        ListIt ti(k, tl);
+                        uint64_t gx = 0, gy = 0;
+                        size_t hl;
+                        const uint8_t* h = ti.next(&hl);
+                        if ((st = half(x, h, hl, &gx))) break;
+                        h = ti.next(&hl);
+                        if ((st = half(y, h, hl, &gy))) break;
+                        if (ti.tail() && ti.tail()[0] != kNil) { st = LASPJ_DEC_MALFORMED; break; }
+                        it->toks.push_back(kPairBit | (gx << 31) | gy | (flag ? kFlagBit : 0ull));
+                    }
+                    if (st == LASPJ_DEC_OK && ci.tail() && ci.tail()[0] != kNil) st = LASPJ_DEC_MALFORMED;
+                }
+                if (st) break;
+                it->keys.push_back(kPairBit | ((uint64_t)x << 31) | y);
+                it->toff.push_back((uint32_t)it->toks.size());
+            }
+            if (st == LASPJ_DEC_OK && li.tail() && li.tail()[0] != kNil) st = LASPJ_DEC_MALFORMED;
+        }
+    } catch (const std::bad_alloc&) {
+        d->rollback();
+        d->journal.clear();
+        return LASPJ_E_NOMEM;
+    }
+    if (st != LASPJ_DEC_OK) d->rollback();
+    d->journal.clear();
+    return st;
+}
+
 int list_register(laspj_dict* dict, const uint8_t* img, size_t n, uint32_t* slot) {
     Dict* d = &dict->d;
     d->journal.clear();

@@ -550,6 +550,12 @@ struct ListItems {
 // or LASPJ_E_NOMEM
 int list_walk(laspj_dict* dict, int32_t kind, const uint8_t* p, size_t n, ListItems* it,
               std::vector<uint32_t>* args);
+// list_walk in pair mode (a pair-keyed list variable's images, include/laspj.h): 131 + a list
+// of {{X, Y}, [{[Tx, Ty], Bool}]} — X and Y registered as elements, Tx as a token of X, Ty as
+// a token of Y; key items bit 62 | x << 31 | y, token items bit 62 | gx << 31 | gy | flag.
+// Anything else (a key that is no 2-tuple, a token that is no proper 2-list: LIST_EXT of two
+// with a NIL tail, or STRING_EXT of two) is refused as list_walk refuses, registrations undone
+int list_walk_pairs(laspj_dict* dict, const uint8_t* p, size_t n, ListItems* it);
 // register one term image (no version byte) as an element; a LASPJ_DEC_* status
 int list_register(laspj_dict* dict, const uint8_t* img, size_t n, uint32_t* slot);
 std::string_view list_elem_image(const laspj_dict* dict, uint32_t e);
@@ -770,6 +776,36 @@ constexpr uint32_t kLvTile = 1024;      // positions per block: 256 threads x 4
 inline uint32_t lv_isect_tiles(uint32_t n) { return n ? (n + kLvTile - 1) / kLvTile : 1; }
 hipError_t launch_lv_isect(laspj_ctx* ctx, const LvIsect& a, const ListDev& out, uint64_t* tiles,
                            uint32_t* ans);
+// product/7's OR-Set branch (lasp_core.erl:499-533, lasp_lattice.erl:303-308) from two
+// variables' cells.  The side pass (two launches in the k_lv_count / k_lv_write tile scheme,
+// one side per blockIdx.y; tiles: 2 x lv_isect_tiles(n) C2 pairs) compacts each side's held
+// positions (p != 0, tombstoned or not) in term order: slot[i] the element slot, tpre[i] the
+// exclusive token prefix (tpre[held] the total), run[tpre[i] ..] the tokens in term order
+// (lv_run: 64 e + k, bit 63 removed), own[t] the position token t belongs to.  Its last tile
+// per side writes ans[2 s] = held, ans[2 s + 1] = tokens, ans[4 + s] = 1 when cap_t was short.
+// The host reads the four totals and sizes the output; the write pass then needs no scan:
+// entry o = i nr + j has key {x_i, y_j}, toff[o] = A_i TR + a_i B_j, and output token t of
+// NT = TL TR finds (i, j, u, v) through own in O(1) — one key / toff word and one token word
+// per thread, consecutive lanes on consecutive words, every index product 64-bit.  Its last
+// block writes the header and the toff sentinel (ans[6] = 1, the empty list: out was short).
+struct LvSide {
+    const uint64_t* cells;
+    uint32_t E;                         // element slots the cells cover
+    uint32_t* slot;                     // n words
+    uint32_t* tpre;                     // n + 1 words
+    uint32_t* own;                      // cap_t words
+    uint64_t* run;                      // cap_t words
+};
+struct LvProd {
+    LvSide s[2];                        // l, r
+    const uint32_t* elem_order;
+    uint32_t n;                         // term-order positions
+    uint32_t cap_t;                     // tokens a side's run and own arrays hold
+    const uint32_t* grank;              // 64 words per element slot
+};
+hipError_t launch_lp_sides(laspj_ctx* ctx, const LvProd& a, uint64_t* tiles, uint32_t* ans);
+hipError_t launch_lp_write(laspj_ctx* ctx, const LvProd& a, uint32_t nl, uint32_t nr, uint32_t TL,
+                           uint32_t TR, const ListDev& out, uint32_t* ans);
 // map/6's body (lasp_core.erl:641-667) from one variable's cells and a map process's tables
 // (include/laspj.h "resident map processes"): per term-order position j < n, e =
 // elem_order[j]; a held cell (any token, tombstoned ones too) of an evaluated slot whose

@@ -24,7 +24,9 @@
 // map/6 (lasp_core.erl:641-667; include/laspj.h "resident map processes") is the same producer
 // over one variable's cells and a map process's tables: k_lm_count / k_lm_write below; fold/6
 // (lasp_core.erl:460-486; "resident fold processes") emits a run of entries per cell:
-// k_lf_count / k_lf_write.
+// k_lf_count / k_lf_write.  product/7 (lasp_core.erl:499-533; "pair-keyed list variables")
+// compacts both inputs' cells the same way (k_lp_count / k_lp_side) and writes the |L| x |R|
+// output from the two sides' prefixes without a scan (k_lp_write).
 
 #include "laspj_internal.h"
 
@@ -513,6 +515,138 @@ __global__ __launch_bounds__(kLvT) void k_lf_write(LfFold a, ListDev out, const 
     }
 }
 
+// ---- product/7 (lasp_core.erl:499-533) from two variables' cells --------------------------
+// AccValue = [{{X, Y}, orset_causal_product(Cx, Cy)} || {X, Cx} <- L, {Y, Cy} <- R]
+// (lasp_lattice.erl:303-308: both foldls reversed).  The side pass compacts each side's held
+// positions; with held counts nl, nr and token totals TL, TR the output is a closed form of
+// the two sides' prefixes, so the write pass scans nothing (LvProd, laspj_internal.h).
+
+constexpr u64 kLvPair = 1ull << 62;           // a pair key {X, Y} / a 2-list token [Tx, Ty]
+constexpr u64 kLvId = 0x7FFFFFFFull;
+
+__device__ __forceinline__ u64x2 lp_cell(const LvSide& s, uint32_t e) {
+    if (e >= s.E) return u64x2{0, 0};
+    return *reinterpret_cast<const u64x2*>(s.cells + 2ull * e);
+}
+
+__global__ __launch_bounds__(kLvT) void k_lp_count(LvProd a, u64* tiles) {
+    __shared__ Cnt lds[kLvT / 64];
+    const LvSide& s = a.s[blockIdx.y];
+    const uint32_t j0 = blockIdx.x * kLvTile + threadIdx.x * kLvI;
+    uint32_t e[kLvI];
+    lv_slots(a, j0, e);
+    Cnt mine{0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        const u64x2 C = lp_cell(s, e[k]);
+        if (!C.x) continue;
+        mine.e += 1;
+        mine.t += (uint32_t)__popcll(C.x);
+    }
+    Cnt tot;
+    lv_block_excl(mine, lds, &tot);
+    if (threadIdx.x == 0) {
+        const u64 at = (u64)blockIdx.y * gridDim.x + blockIdx.x;
+        tiles[2 * at] = tot.e;
+        tiles[2 * at + 1] = tot.t;
+    }
+}
+
+__global__ __launch_bounds__(kLvT) void k_lp_side(LvProd a, const u64* tiles, uint32_t* ans) {
+    __shared__ Cnt lds[kLvT / 64];
+    const LvSide& s = a.s[blockIdx.y];
+    const u64* mine_tiles = tiles + 2ull * blockIdx.y * gridDim.x;
+    Cnt pre{0, 0};
+    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += kLvT) {
+        pre.e += (uint32_t)mine_tiles[2ull * i];
+        pre.t += (uint32_t)mine_tiles[2ull * i + 1];
+    }
+    Cnt base;
+    lv_block_excl(pre, lds, &base);
+    const uint32_t j0 = blockIdx.x * kLvTile + threadIdx.x * kLvI;
+    uint32_t e[kLvI];
+    lv_slots(a, j0, e);
+    u64x2 C[kLvI];
+    Cnt mine{0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        C[k] = lp_cell(s, e[k]);
+        if (!C[k].x) continue;
+        mine.e += 1;
+        mine.t += (uint32_t)__popcll(C[k].x);
+    }
+    Cnt tot;
+    const Cnt ex = lv_block_excl(mine, lds, &tot);
+    uint32_t pos = base.e + ex.e, tp = base.t + ex.t;
+#pragma unroll
+    for (uint32_t k = 0; k < kLvI; ++k) {
+        if (!C[k].x) continue;
+        const uint32_t c = (uint32_t)__popcll(C[k].x);
+        // (held positions are at most n; the token arrays hold cap_t)
+        if (pos < a.n && (u64)tp + c <= a.cap_t) {
+            s.slot[pos] = e[k];
+            s.tpre[pos] = tp;
+            lv_run(s.run + tp, e[k], C[k].x, C[k].y, a.grank + 64ull * e[k]);
+            for (uint32_t t = 0; t < c; ++t) s.own[tp + t] = pos;
+        }
+        pos += 1;
+        tp += c;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        const uint32_t ne = base.e + tot.e, nt = base.t + tot.t;
+        const bool over = ne > a.n || nt > a.cap_t;
+        if (!over) s.tpre[ne] = nt;
+        ans[2 * blockIdx.y] = ne;
+        ans[2 * blockIdx.y + 1] = nt;
+        ans[4 + blockIdx.y] = over ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lp_write(LvProd a, uint32_t nl, uint32_t nr, uint32_t TL,
+                                                  uint32_t TR, ListDev out, uint32_t* ans) {
+    const LvSide& L = a.s[0];
+    const LvSide& R = a.s[1];
+    const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
+    const u64 NE = (u64)nl * nr, NT = (u64)TL * TR;
+    const bool over = NE > out.ce || NT > out.ct;
+    if (!over && g < NE) {
+        // entry o = i nr + j: l-major, the term order of the 2-tuples
+        const uint32_t i = (uint32_t)(g / nr), j = (uint32_t)(g - (u64)i * nr);
+        const uint32_t Ai = L.tpre[i], ai = L.tpre[i + 1] - Ai;
+        out.key[g] = kLvPair | ((u64)(L.slot[i] & kLvId) << 31) | (R.slot[j] & kLvId);
+        out.toff[g] = (uint32_t)((u64)Ai * TR + (u64)ai * R.tpre[j]);
+    }
+    if (!over && g < NT) {
+        // token g: l's token g / TR names i; inside i's rows r's token rem / a_i names j
+        const uint32_t q = (uint32_t)(g / TR);
+        const uint32_t i = L.own[q];
+        if (i < nl) {
+            const uint32_t Ai = L.tpre[i], ai = L.tpre[i + 1] - Ai;
+            const u64 rem = g - (u64)Ai * TR;
+            const uint32_t m = ai ? (uint32_t)(rem / ai) : TR;
+            const uint32_t j = m < TR ? R.own[m] : nr;
+            if (j < nr) {
+                const uint32_t Bj = R.tpre[j], bj = R.tpre[j + 1] - Bj;
+                const u64 w = rem - (u64)ai * Bj;            // inside the a_i b_j run
+                const uint32_t u = bj ? (uint32_t)(w / bj) : ai;
+                if (u < ai) {
+                    const uint32_t v = (uint32_t)(w - (u64)u * bj);
+                    // both runs reversed, as the double foldl leaves them
+                    const u64 X = L.run[Ai + (ai - 1 - u)], Y = R.run[Bj + (bj - 1 - v)];
+                    out.tok[g] = kLvPair | ((X & kLvId) << 31) | (Y & kLvId) |
+                                 ((X | Y) & kLvRemoved);     // XDeleted orelse YDeleted
+                }
+            }
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        out.hdr[0] = over ? 0u : (uint32_t)NE;
+        out.hdr[1] = over ? 0u : (uint32_t)NT;
+        out.toff[over ? 0u : (uint32_t)NE] = over ? 0u : (uint32_t)NT;
+        ans[6] = over ? 1u : 0u;
+    }
+}
+
 // one wave per element slot: lane j reads the slot of term-order place j of its tokens
 __global__ __launch_bounds__(256) void k_lv_ranks(const uint32_t* __restrict__ elem_order,
                                                   const uint8_t* __restrict__ tok_order, uint32_t E,
@@ -550,6 +684,21 @@ hipError_t launch_lv_isect(laspj_ctx* ctx, const LvIsect& a, const ListDev& out,
     const uint32_t ntile = lv_isect_tiles(a.n);
     hipLaunchKernelGGL(k_lv_count, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, tiles);
     hipLaunchKernelGGL(k_lv_write, dim3(ntile), dim3(kLvT), 0, ctx->stream, a, out, tiles, ans);
+    return hipGetLastError();
+}
+
+hipError_t launch_lp_sides(laspj_ctx* ctx, const LvProd& a, uint64_t* tiles, uint32_t* ans) {
+    const dim3 grid(lv_isect_tiles(a.n), 2);
+    hipLaunchKernelGGL(k_lp_count, grid, dim3(kLvT), 0, ctx->stream, a, tiles);
+    hipLaunchKernelGGL(k_lp_side, grid, dim3(kLvT), 0, ctx->stream, a, tiles, ans);
+    return hipGetLastError();
+}
+
+hipError_t launch_lp_write(laspj_ctx* ctx, const LvProd& a, uint32_t nl, uint32_t nr, uint32_t TL,
+                           uint32_t TR, const ListDev& out, uint32_t* ans) {
+    const uint64_t span = std::max<uint64_t>({(uint64_t)nl * nr, (uint64_t)TL * TR, 1});
+    hipLaunchKernelGGL(k_lp_write, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, ctx->stream,
+                       a, nl, nr, TL, TR, out, ans);
     return hipGetLastError();
 }
 

@@ -1663,6 +1663,7 @@ void nif_destroy(laspj_ctx* ctx) {
     if (S->rd_d) hipFree(S->rd_d);
     if (S->rd_h) hipHostFree(S->rd_h);
     if (S->lv_tiles) hipFree(S->lv_tiles);
+    if (S->lp_side) hipFree(S->lp_side);
     if (S->lv_ans) hipHostFree(S->lv_ans);
     for (const PinSlot& p : S->pins) hipHostFree(p.h);
     delete S;

@@ -646,6 +646,8 @@ int laspj_fold_create(laspj_var* in, laspj_lvar* out, laspj_fold** f) {
     if (!S->vars.count(in) || !S->lvars.count(out)) return laspj::unknown_variable(ctx, "fold_create");
     if (in->kind != LASPJ_KIND_ORSET)
         return fail(ctx, LASPJ_E_KIND, "fold_create: an OR-Set variable (a list variable holds OR-Set lists)");
+    if (out->pairs)
+        return fail(ctx, LASPJ_E_KIND, "fold_create: a pair-keyed list variable takes product/7's output only");
     if (in->ns != out->ns)
         return fail(ctx, LASPJ_E_UNSUPPORTED, "fold_create: variables of one namespace");
     auto* p = new (std::nothrow) laspj_fold;

@@ -170,6 +170,8 @@ struct laspj_lvar {
     uint64_t epoch = 0;              // the dictionary generation the items refer to
     bool resident = true;            // `list` holds the value (else `image` does)
     bool held = false;               // `image` is a value the walk refused (until the next write)
+    bool pairs = false;              // pair-keyed (laspj_lvar_create_pairs): every image of it
+                                     // is walked by list_walk_pairs, for its whole life
     laspj_batch* list = nullptr;
     laspj_batch* val = nullptr;
     laspj_batch* dst = nullptr;
@@ -380,6 +382,10 @@ struct NifState {
     uint64_t lv_tiles_bytes = 0;
     uint32_t* lv_ans = nullptr;
     uint32_t* lv_ans_d = nullptr;
+    // the product's side arrays (laspj_lvar_product: per side the held slots, the exclusive
+    // token prefix, the runs in term order and each token's owner position)
+    void* lp_side = nullptr;
+    uint64_t lp_side_bytes = 0;
     std::unordered_set<laspj_map*> maps;         // the live map processes
     std::unordered_set<laspj_fold*> folds;       // the live fold processes
 };

@@ -25,6 +25,13 @@ void llazy_clear(laspj_lvar* lv) {
     lv->lazy.clear();
 }
 
+// an image of the variable walked in its mode: pair-keyed variables take
+// [{{X, Y}, [{[Tx, Ty], Bool}]}] (list_walk_pairs), the others list_walk's OR-Set lists
+int lvar_walk_image(laspj_dict* dict, bool pairs, const uint8_t* p, size_t n, ListItems* it) {
+    return pairs ? list_walk_pairs(dict, p, n, it)
+                 : list_walk(dict, LASPJ_KIND_ORSET, p, n, it, nullptr);
+}
+
 namespace {
 
 // the list of a one-replica batch as items (list order)
@@ -146,8 +153,7 @@ int lvar_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, bool* ok) {
         if (int s = reset_dict(ctx, S, K)) return s;
     const RegMark m = reg_mark(K);
     ListItems it;
-    const int st = list_walk(K.dict, LASPJ_KIND_ORSET, lv->image.data(), lv->image.size(), &it,
-                             nullptr);
+    const int st = lvar_walk_image(K.dict, lv->pairs, lv->image.data(), lv->image.size(), &it);
     if (st == LASPJ_E_NOMEM) return fail(ctx, LASPJ_E_NOMEM, "lvar: host allocation");
     if (st != LASPJ_DEC_OK) {
         lv->held = true;
@@ -183,6 +189,8 @@ int lvar_bind(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, int32_t* status,
     const LvOrder ord(ctx, *lv->ns);
     uint8_t st = 0;
     const uint64_t t0 = now_ns();
+    // (pair keys have no rank universe: straight to the general bind, no rank-indexed try)
+    if (lv->pairs) lv->list->not_asc = lv->val->not_asc = true;
     if (int s = list_bind_tail(ctx, lv->dst, lv->list, lv->val, &ord.o, &st,
                                tail ? tail->data() : nullptr, tail ? (uint32_t)tail->size() : 0,
                                met))
@@ -227,8 +235,9 @@ int lvar_intersection_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj
     *status = LASPJ_BIND_NOOP;
     *verdict = LASPJ_NIF_FALLBACK;
     // OR-Sets of the list's namespace only: cells of another namespace name other terms
-    if (l->kind != LASPJ_KIND_ORSET || r->kind != LASPJ_KIND_ORSET || l->ns != out->ns ||
-        r->ns != out->ns)
+    // (a pair-keyed variable takes product/7's output only)
+    if (out->pairs || l->kind != LASPJ_KIND_ORSET || r->kind != LASPJ_KIND_ORSET ||
+        l->ns != out->ns || r->ns != out->ns)
         return fallback(S);
     KindState& K = *out->ns;
     if (K.wide) return fallback(S);
@@ -308,6 +317,91 @@ int lvar_intersection_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj
     return LASPJ_OK;
 }
 
+// laspj_lvar_product with S->mu held and the handles checked
+int lvar_product_locked(laspj_ctx* ctx, NifState* S, laspj_lvar* out, laspj_var* l, laspj_var* r,
+                        int32_t* status, int32_t* verdict,
+                        const std::vector<ListWaiter>* tail = nullptr, uint8_t* met = nullptr) {
+    ++S->stats[ST_CALLS];
+    *status = LASPJ_BIND_NOOP;
+    *verdict = LASPJ_NIF_FALLBACK;
+    if (!out->pairs || l->kind != LASPJ_KIND_ORSET || r->kind != LASPJ_KIND_ORSET ||
+        l->ns != out->ns || r->ns != out->ns)
+        return fallback(S);
+    KindState& K = *out->ns;
+    if (K.wide) return fallback(S);
+    for (laspj_var* v : {l, r}) {
+        bool ok = false;
+        if (int s = hydrate(ctx, S, v, &ok)) return s;
+        if (!ok) return fallback(S);
+    }
+    bool ok = false;
+    if (int s = lvar_ready(ctx, S, out, &ok)) return s;
+    // (a decode above may have widened the namespace or started its dictionary afresh)
+    if (!ok || K.wide || !var_current(l) || !var_current(r) || out->epoch != K.epoch)
+        return fallback(S);
+    *verdict = LASPJ_NIF_OK;
+    if (!K.dict || dict_elements(K.dict) == 0) return LASPJ_OK;      // three empty values
+    if (int s = lvar_images(ctx, S, K)) return s;
+    const uint32_t n = K.built_K;
+    const uint64_t cap_t = std::max<uint64_t>(K.built_toks, 1);
+    if (cap_t > 0xFFFFFFF0ull) return fail(ctx, LASPJ_E_RANGE, "lvar_product: too many tokens");
+    const uint64_t t0 = now_ns();
+    {
+        Guard g(ctx);
+        if (int s = lvar_ranks(ctx, S, K)) return s;
+        const uint32_t ntile = lv_isect_tiles(n);
+        if (int s = lvar_scratch(ctx, S, 2 * ntile)) return s;
+        // per side: [slot n | tpre n + 1 | own cap_t] words (to 8 bytes), then run cap_t u64
+        const uint64_t words = ((uint64_t)n + (n + 1ull) + cap_t + 1) & ~1ull;
+        const uint64_t side = 4 * words + 8 * cap_t;
+        if (int s = grow_dev(ctx, &S->lp_side, &S->lp_side_bytes, 2 * side)) return s;
+        LvProd a;
+        for (int k = 0; k < 2; ++k) {
+            const laspj_var* v = k ? r : l;
+            char* base = static_cast<char*>(S->lp_side) + k * side;
+            a.s[k].cells = v->cells;
+            a.s[k].E = v->cells ? v->E : 0;
+            a.s[k].slot = reinterpret_cast<uint32_t*>(base);
+            a.s[k].tpre = a.s[k].slot + n;
+            a.s[k].own = a.s[k].tpre + n + 1;
+            a.s[k].run = reinterpret_cast<uint64_t*>(base + 4 * words);
+        }
+        a.elem_order = etf_dict_elem_order(K.etf);
+        a.n = n;
+        a.cap_t = (uint32_t)cap_t;
+        a.grank = static_cast<const uint32_t*>(K.grank);
+        S->lv_ans[4] = S->lv_ans[5] = 2;                    // (not written yet)
+        LJ_HIP(ctx, launch_lp_sides(ctx, a, static_cast<uint64_t*>(S->lv_tiles), S->lv_ans_d));
+        // the one small synchronisation the sizes cost: |L| x |R| has no useful a-priori bound
+        LJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (S->lv_ans[4] != 0 || S->lv_ans[5] != 0)
+            return fail(ctx, LASPJ_E_RANGE, "lvar_product: a side's token bound did not hold "
+                        "(%u and %u tokens)", S->lv_ans[1], S->lv_ans[3]);
+        const uint32_t nl = S->lv_ans[0], TL = S->lv_ans[1], nr = S->lv_ans[2], TR = S->lv_ans[3];
+        const uint64_t NE = (uint64_t)nl * nr, NT = (uint64_t)TL * TR;
+        if (NE > 0xFFFFFFF0ull || NT > 0xFFFFFFF0ull)
+            return fail(ctx, LASPJ_E_RANGE, "lvar_product: %llu entries, %llu tokens",
+                        (unsigned long long)NE, (unsigned long long)NT);
+        if (int s = list_reserve(ctx, out->val, (uint32_t)std::max<uint64_t>(NE, 1),
+                                 (uint32_t)std::max<uint64_t>(NT, 1)))
+            return s;
+        S->lv_ans[6] = 2;
+        LJ_HIP(ctx, launch_lp_write(ctx, a, nl, nr, TL, TR, list_dev(out->val), S->lv_ans_d));
+        out->val->known_e = (uint32_t)NE;
+        out->val->known_t = (uint32_t)NT;
+        out->val->not_asc = true;           // (pairs: the general bind, see lvar_bind)
+        out->val->no_spec = false;
+    }
+    S->stats[ST_NS_ENQUEUE] += now_ns() - t0;
+    int32_t st = 0;
+    if (int s = lvar_bind(ctx, S, out, &st, tail, met)) return s;
+    if (S->lv_ans[6] != 0)
+        return fail(ctx, LASPJ_E_RANGE, "lvar_product: the output's capacity did not hold");
+    if (st == LASPJ_BIND_WRITTEN) llazy_clear(out);      // write/4: a fresh #dv (:842-843)
+    *status = st;
+    return LASPJ_OK;
+}
+
 // an image walked into lv->val over the namespace (its unseen terms registered, the images
 // and tables brought up to them); *ok false: the walk refused it (its registrations undone)
 // into (or null: lv->val): the list that takes the items
@@ -320,7 +414,7 @@ int lvar_walk_val(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, const uint8_t* p,
     const RegMark m = reg_mark(K);
     ListItems it;
     const uint64_t t0 = now_ns();
-    const int st = list_walk(K.dict, LASPJ_KIND_ORSET, p, n, &it, nullptr);
+    const int st = lvar_walk_image(K.dict, lv->pairs, p, n, &it);
     S->stats[ST_NS_REGISTER] += now_ns() - t0;
     if (st == LASPJ_E_NOMEM) return fail(ctx, LASPJ_E_NOMEM, "lvar: host allocation");
     if (st != LASPJ_DEC_OK) return LASPJ_OK;
@@ -385,8 +479,7 @@ int lentries_ready(laspj_ctx* ctx, NifState* S, laspj_lvar* lv, std::vector<LWai
             if (int s = reset_dict(ctx, S, K)) return s;
         const RegMark m = reg_mark(K);
         ListItems it;
-        const int st = list_walk(K.dict, LASPJ_KIND_ORSET, w.image.data(), w.image.size(), &it,
-                                 nullptr);
+        const int st = lvar_walk_image(K.dict, lv->pairs, w.image.data(), w.image.size(), &it);
         if (st == LASPJ_E_NOMEM) return fail(ctx, LASPJ_E_NOMEM, "lvar: host allocation");
         if (st != LASPJ_DEC_OK) {
             *ok = false;
@@ -481,11 +574,8 @@ void lvar_free_batches(laspj_lvar* lv) {
     for (laspj::LWaiter& z : lv->lazy) laspj::lwaiter_release(z);
 }
 
-}  // namespace
-
-extern "C" {
-
-int laspj_lvar_create(laspj_var* peer, laspj_lvar** out) {
+// laspj_lvar_create / laspj_lvar_create_pairs
+int lvar_create(laspj_var* peer, laspj_lvar** out, bool pairs) {
     if (!peer || !out) return LASPJ_E_INVAL;
     *out = nullptr;
     if (peer->gc) {
@@ -503,6 +593,7 @@ int laspj_lvar_create(laspj_var* peer, laspj_lvar** out) {
     lv->ctx = ctx;
     lv->ns = peer->ns;
     lv->epoch = peer->ns->epoch;
+    lv->pairs = pairs;
     for (laspj_batch** b : {&lv->list, &lv->val, &lv->dst})
         if (int s = laspj_list_batch_create(ctx, LASPJ_KIND_ORSET_LIST, 1, 1, 1, b)) {
             lvar_free_batches(lv);
@@ -528,6 +619,16 @@ int laspj_lvar_create(laspj_var* peer, laspj_lvar** out) {
     lv->ns->rank_full = true;
     *out = lv;
     return LASPJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int laspj_lvar_create(laspj_var* peer, laspj_lvar** out) { return lvar_create(peer, out, false); }
+
+int laspj_lvar_create_pairs(laspj_var* peer, laspj_lvar** out) {
+    return lvar_create(peer, out, true);
 }
 
 int laspj_lvar_destroy(laspj_lvar* lv) {
@@ -815,6 +916,69 @@ int laspj_lvar_intersection_recheck(laspj_lvar* out, laspj_var* l, laspj_var* r,
         std::vector<uint8_t> met(ws.size(), 0);
         if (int s = laspj::lvar_intersection_locked(ctx, S, out, l, r, status, verdict,
                                                     tail ? &ws : nullptr, met.data()))
+            return s;
+        // NOOP, REFUSED, FALLBACK: the value is as it was, so no registered waiter became met
+        if (*verdict != LASPJ_NIF_OK || *status != LASPJ_BIND_WRITTEN || out->waiters.empty())
+            return LASPJ_OK;
+        if (!tail) {
+            // written, the waiters not checked (an image the walk refuses): the NIF's walk
+            *verdict = LASPJ_NIF_FALLBACK;
+            return laspj::fallback(S);
+        }
+        laspj::lwaiters_take(out, met.data(), ids, cap, nmet);
+        *nwaiting = (uint32_t)out->waiters.size();
+        return LASPJ_OK;
+    });
+}
+
+int laspj_lvar_product(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                       int32_t* verdict) {
+    if (!l || !r) return LASPJ_E_INVAL;
+    const laspj::Entry e = enter_lvar(out, "lvar_product", status && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    *status = LASPJ_BIND_NOOP;
+    *verdict = LASPJ_NIF_FALLBACK;
+    if (l->gc || r->gc || l->ctx != ctx || r->ctx != ctx || !S->vars.count(l) || !S->vars.count(r)) {
+        // a counter, a variable of another context: nothing this body runs over
+        ++S->stats[laspj::ST_CALLS];
+        return laspj::fallback(S);
+    }
+    return laspj::nomem_guard(ctx, "lvar_product", [&] {
+        return laspj::lvar_product_locked(ctx, S, out, l, r, status, verdict);
+    });
+}
+
+int laspj_lvar_product_recheck(laspj_lvar* out, laspj_var* l, laspj_var* r, int32_t* status,
+                               uint64_t* ids, uint32_t cap, uint32_t* nmet, uint32_t* nwaiting,
+                               int32_t* verdict) {
+    if (!l || !r) return LASPJ_E_INVAL;
+    const laspj::Entry e = enter_lvar(out, "lvar_product_recheck",
+                                      status && (ids || !cap) && nmet && nwaiting && verdict);
+    if (e.rc) return e.rc;
+    laspj::NifState* S = e.S;
+    laspj_ctx* ctx = e.ctx;
+    *status = LASPJ_BIND_NOOP;
+    *verdict = LASPJ_NIF_FALLBACK;
+    *nmet = 0;
+    *nwaiting = (uint32_t)out->waiters.size();
+    if (l->gc || r->gc || l->ctx != ctx || r->ctx != ctx || !S->vars.count(l) || !S->vars.count(r)) {
+        ++S->stats[laspj::ST_CALLS];
+        return laspj::fallback(S);
+    }
+    return laspj::nomem_guard(ctx, "lvar_product_recheck", [&]() -> int {
+        // the waiters' thresholds on the device first, as laspj_lvar_intersection_recheck
+        bool ok = false, wok = false;
+        if (int s = laspj::lvar_ready(ctx, S, out, &ok)) return s;
+        if (ok)
+            if (int s = laspj::lwaiters_ready(ctx, S, out, &wok)) return s;
+        const bool tail = wok && !out->waiters.empty();
+        const std::vector<laspj::ListWaiter> ws =
+            tail ? laspj::lwaiter_descs(out) : std::vector<laspj::ListWaiter>();
+        std::vector<uint8_t> met(ws.size(), 0);
+        if (int s = laspj::lvar_product_locked(ctx, S, out, l, r, status, verdict,
+                                               tail ? &ws : nullptr, met.data()))
             return s;
         // NOOP, REFUSED, FALLBACK: the value is as it was, so no registered waiter became met
         if (*verdict != LASPJ_NIF_OK || *status != LASPJ_BIND_WRITTEN || out->waiters.empty())

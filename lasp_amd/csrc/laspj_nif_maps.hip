@@ -538,6 +538,8 @@ int laspj_map_create(laspj_var* in, laspj_lvar* out, laspj_map** m) {
     if (!S->vars.count(in) || !S->lvars.count(out)) return laspj::unknown_variable(ctx, "map_create");
     if (in->kind != LASPJ_KIND_ORSET)
         return fail(ctx, LASPJ_E_KIND, "map_create: an OR-Set variable (a list variable holds OR-Set lists)");
+    if (out->pairs)
+        return fail(ctx, LASPJ_E_KIND, "map_create: a pair-keyed list variable takes product/7's output only");
     if (in->ns != out->ns)
         return fail(ctx, LASPJ_E_UNSUPPORTED, "map_create: variables of one namespace");
     auto* p = new (std::nothrow) laspj_map;

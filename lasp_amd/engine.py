@@ -241,6 +241,12 @@ class Context:
         namespace (what the combinator bodies bind: `{X, Cx ++ Cy}`, repeated keys)."""
         return NifListVar(self, peer)
 
+    def pair_list_var(self, peer: "NifVar") -> "NifListVar":
+        """laspj_lvar_create_pairs: a pair-keyed list variable holding [] in peer's namespace
+        (what product/7 binds: `{{X, Y}, [{[Tx, Ty], Bool}]}`); its images are walked in pair
+        mode for its whole life."""
+        return NifListVar(self, peer, pairs=True)
+
     def map(self, in_var: "NifVar", out_lvar: "NifListVar") -> "NifMap":
         """laspj_map_create: a resident lasp_process running map/6 from the OR-Set in_var
         into the list variable out_lvar (one namespace)."""
@@ -596,10 +602,35 @@ class NifListVar:
     ...) like the variable calls; bind statuses are 0 no-op, 1 written, 2 refused (the merge
     does not inflate the value: nothing written)."""
 
-    def __init__(self, ctx: Context, peer: NifVar):
+    def __init__(self, ctx: Context, peer: NifVar, pairs: bool = False):
         self.ctx, self.L = ctx, ctx.L
         self.h = C.c_void_p()
-        check(self.L.laspj_lvar_create(peer.h, C.byref(self.h)), ctx.h)
+        self.pairs = pairs
+        make = self.L.laspj_lvar_create_pairs if pairs else self.L.laspj_lvar_create
+        check(make(peer.h, C.byref(self.h)), ctx.h)
+
+    def product(self, left: NifVar, right: NifVar):
+        """laspj_lvar_product: product/7's OR-Set branch over resident left / right bound into
+        this pair-keyed variable — (verdict, status)."""
+        st, verd = C.c_int32(), C.c_int32()
+        check(self.L.laspj_lvar_product(self.h, left.h, right.h, C.byref(st), C.byref(verd)),
+              self.ctx.h)
+        return int(verd.value), int(st.value)
+
+    def product_recheck(self, left: NifVar, right: NifVar, cap: int = 16):
+        """laspj_lvar_product_recheck: the product's re-run and, when it writes, the waiters'
+        re-check inside the bind's synchronisation — (verdict, status, [ids met, in list
+        order], waiters left), as intersection_recheck answers."""
+        ids = (C.c_uint64 * max(cap, 1))()
+        st, nmet, left_n, verd = C.c_int32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        check(self.L.laspj_lvar_product_recheck(self.h, left.h, right.h, C.byref(st), ids, cap,
+                                                C.byref(nmet), C.byref(left_n),
+                                                C.byref(verd)), self.ctx.h)
+        if nmet.value > cap:
+            verd2, got, n = self.recheck(nmet.value)
+            return verd2, int(st.value), got, n
+        return int(verd.value), int(st.value), [int(x) for x in ids[:nmet.value]], \
+            int(left_n.value)
 
     def intersection(self, left: NifVar, right: NifVar):
         """laspj_lvar_intersection: intersection/7's OR-Set branch over resident left / right
